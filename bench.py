@@ -30,6 +30,15 @@ HBM bytes per launch (profiles/traffic_*.json).  `path_roofline` is B_alg x reco
 A `host_fed` leg (rank 0, N = 1) pushes further batches from pinned host memory through fw_push_batch and
 drains the fired rows to the host: the PCIe-inclusive rate of the JNI drop-in, reported beside `value`.
 
+The timed steps' batches are staged in HBM a chunk at a time (`--stage-gib`, 158 steps at C2's defaults): a longer run
+stops its clock at a chunk's end, generates the next chunk and goes on, so `--steps` is bounded by time, not by HBM.
+A plain run sets up, warms up, times the `--steps` steps and prints the line (value, ms_per_step, the timed region's
+own kernel figures).  The legs that take runs of their own come with `--full`: the isolated per-kernel pass
+(`kernels_isolated`, `roofline.isolated`), `host_fed`, C1's `count_window_gpu` and `cpu_baseline`.
+`--dump-outputs DIR` writes what the timed path computed as DIR/<name>.npy (float64; dump_outputs()): the rows the
+last timed step fired and the rows the windows still live after the run fire under a final watermark.  The stream is
+counter-based, so two runs with the same arguments see identical inputs.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -280,6 +289,15 @@ def main():
                          "multi-rank bench path; RCCL cannot put two ranks on one GPU)")
     ap.add_argument("--sync-input", action="store_true",
                     help="partition each batch on the operator's own stream (no overlap with the previous batch)")
+    ap.add_argument("--stage-gib", type=float, default=64.0,
+                    help="HBM for the staged batches of the timed steps (GiB; at most a quarter of the free HBM): more "
+                         "steps than fit are timed chunk by chunk, the clock stopped while the next chunk is generated")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the isolated per-kernel "
+                         "pass, the host-fed (PCIe) leg, C1's count-window leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed as DIR/<name>.npy (float64): the rows its last timed step "
+                         "fired (fired_*) and the rows the live windows it left fire under a final watermark (final_*)")
     args = ap.parse_args()
     if args.combine and args.rehearse_gloo:
         ap.error("--combine with --rehearse-gloo: the gloo rehearsal exchanges records through the Python exchange "
@@ -391,20 +409,47 @@ def main():
             v = v.to(torch.float64)  # the Double field: the generator's int32 values
         return k, t, v, mx, None
 
-    # warmup batches are generated step by step (untimed); the timed ones are staged in HBM up front.
+    # warmup batches are generated step by step (untimed); the timed ones are staged in HBM up front, a chunk of
+    # steps at a time: at most a quarter of the free HBM (and 64 GiB) holds staged batches, and the clock stops while
+    # the next chunk is generated, so any --steps fits.  Up to that many steps (158 at C2) it is one chunk, as before.
     # punctuated watermark of this rank's source after each batch: max ts so far - bound
     batches, local_wm = {}, {}
     m = -(1 << 63)
+    chunk = max(1, min(torch.cuda.mem_get_info(dev)[0] // 4, int(args.stage_gib * (1 << 30))) //
+                (args.batch * (28 if c1 else 24)))
+    if world > 1:  # the ranks stop their clocks at the same steps
+        import torch.distributed as dist
+        cc = torch.tensor([chunk], dtype=torch.int64, device=coll_dev)
+        dist.all_reduce(cc, op=dist.ReduceOp.MIN)
+        chunk = int(cc.item())
+
+    def stage(lo, hi):
+        """Generates the batches of steps lo .. hi - 1 into HBM in place of the staged ones (which no kernel reads any
+        more); local_wm gets each batch's own maximum."""
+        batches.clear()
+        mxs = []
+        for s in range(lo, hi):
+            k, t, v, mx, h = generate(s)
+            batches[s] = (k, t, v, h)
+            mxs.append(mx)
+        for s, x in zip(range(lo, hi), torch.cat(mxs).tolist() if mxs else []):
+            local_wm[s] = int(x)  # this batch's max; fold() makes it the watermark
+
+    def fold(lo, hi):
+        """local_wm of steps lo .. hi - 1: the running maximum of the stream so far, less the bound"""
+        nonlocal m
+        for j in range(lo, hi):
+            m = max(m, local_wm[j])
+            local_wm[j] = m - args.bound
+
     # with async input the timed region overlaps each batch's partitioning with the previous batch's aggregation,
     # so the kernels' own durations are also measured in an isolated pass of as many steps after it
-    iso_steps = args.steps if (not args.no_profile and not args.sync_input) else 0
-    for s in range(args.warmup, steps_total + iso_steps):
-        k, t, v, mx, h = generate(s)
-        batches[s] = (k, t, v, h)
-        local_wm[s] = int(mx.item())  # this batch's max; made cumulative once the warmup's is known
+    # (a run of its own: --full)
+    iso_steps = args.steps if (args.full and not args.no_profile and not args.sync_input) else 0
+    stage(args.warmup, min(args.warmup + chunk, steps_total))  # (folded once the warmup's maximum is known)
     torch.cuda.synchronize()
 
-    def step(s):
+    def step(s, keep=False):
         nonlocal m
         if s < args.warmup:
             k, t, v, mx, h = generate(s)
@@ -426,7 +471,8 @@ def main():
         else:
             op.process_batch(k, t, v, h)            # queued; settles the previous step's sequence
         op.advance_watermark(wm, wait=False)  # queued behind the push
-        op.clear_pending()  # discarding sink: fired rows were materialised in HBM
+        if not keep:
+            op.clear_pending()  # discarding sink: fired rows were materialised in HBM
 
     def barrier():
         if world > 1:
@@ -438,9 +484,7 @@ def main():
         L.fw_profile(op._h, 1)
     for s in range(args.warmup):
         step(s)
-    for j in range(args.warmup, steps_total + iso_steps):  # fold the warmup's running max into the staged batch maxima
-        m = max(m, local_wm[j])
-        local_wm[j] = m - args.bound
+    fold(args.warmup, min(args.warmup + chunk, steps_total))  # the warmup's running max into the staged batch maxima
     if not args.no_profile:
         import ctypes
         # the timed region records events around the warmup's two dominant kernels only: every timed launch adds two
@@ -461,16 +505,25 @@ def main():
                 "bytes_received": exch.bytes_received, "recv_reallocs": 0}
 
     xs0 = exchange_stats() if world > 1 else None
-    barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for s in range(args.warmup, steps_total):
-        step(s)
-    op.synchronize()  # settles the last step (resumes it if it suspended)
-    torch.cuda.synchronize()
-    barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = 0.0
+    for lo in range(args.warmup, steps_total, chunk):
+        hi = min(lo + chunk, steps_total)
+        if lo > args.warmup:  # the next chunk's batches, off the clock
+            stage(lo, hi)
+            fold(lo, hi)
+        barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for s in range(lo, hi):
+            step(s, keep=args.dump_outputs is not None and s == steps_total - 1)  # --dump-outputs: the last rows stay
+        op.synchronize()  # settles the last step (resumes it if it suspended)
+        torch.cuda.synchronize()
+        barrier()
+        elapsed += time.perf_counter() - t0
     st1 = op.stats()
+    last_rows = None
+    if args.dump_outputs is not None:
+        last_rows = op.drain_rows()  # what the last timed step fired (the earlier steps' rows were discarded)
 
     exchange = None
     if world > 1:
@@ -575,9 +628,13 @@ def main():
         op.set_async_input(False)  # (synchronizes)
         L.fw_profile(op._h, 1)  # every kind in the isolated pass
         L.fw_profile_read(op._h, None, None, 1)
-        for s in range(steps_total, steps_total + iso_steps):
-            step(s)
-        op.synchronize()
+        for lo in range(steps_total, steps_total + iso_steps, chunk):
+            hi = min(lo + chunk, steps_total + iso_steps)
+            stage(lo, hi)
+            fold(lo, hi)
+            for s in range(lo, hi):
+                step(s)
+            op.synchronize()
         ms_i = (ctypes.c_double * N.FW_NUM_KERNELS)()
         nl_i = (ctypes.c_int64 * N.FW_NUM_KERNELS)()
         L.fw_profile_read(op._h, ms_i, nl_i, 1)
@@ -597,7 +654,7 @@ def main():
                                              "(no overlap): the kernel's duration alone on the GPU"}
 
     count_gpu = None
-    if c1 and world == 1:
+    if args.full and c1 and world == 1:
         count_gpu = count_window_leg(args, batches, local_rank)
 
     host_fed = None
@@ -607,12 +664,22 @@ def main():
         period = args.slide if sliding else (1 if sessions else args.window)
         event_ms = args.batch * 1000.0 / args.rate
         args.host_fed_steps = int(min(12, max(3, (period + args.bound) / event_ms + 2)))
-    if rank == 0 and world == 1 and args.host_fed_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.host_fed_steps > 0:
         host_fed = host_fed_leg(args, op, generate, steps_total + iso_steps, m, c1)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
+
+    outputs = None
+    if args.dump_outputs is not None:
+        # the live windows the run left, fired by a final watermark (plain run: the state after the timed steps)
+        op.synchronize()
+        op.clear_pending()
+        op.advance_watermark((1 << 63) - 1)
+        outputs = dump_outputs(args.dump_outputs, {"fired": last_rows, "final": op.drain_rows()},
+                               ("sum", "min", "max") if tdig else ("sum",) if hll else (), ("max",) if hll else (),
+                               rank, world)
 
     if rank == 0:
         line = {
@@ -643,6 +710,7 @@ def main():
             "host_fed": host_fed,
             **({"count_window_gpu": count_gpu} if count_gpu else {}),
             "cpu_baseline": cpu,
+            **({"outputs": outputs} if outputs else {}),
             "kernels": kernels,
             **({"kernels_isolated": kernels_iso} if kernels_iso else {}),
             "state": {"single_pass_batches": int(st1["single_pass_batches"] - st0["single_pass_batches"]),
@@ -657,6 +725,43 @@ def main():
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
+
+
+DUMP_BUDGET = 60_000_000  # bytes of .npy data one --dump-outputs run writes, all ranks together (< 64 MB)
+
+
+def dump_outputs(out_dir, groups, f64_fields, wide_fields, rank, world):
+    """--dump-outputs: each group of rows ({name: ROW_DTYPE array}) sorted by (key, start) -- the table's order is no
+    part of the result -- and written column by column as <name>_<field>.npy in float64.  f64_fields hold f64 bits
+    (the t-digest's quantiles, the HyperLogLog estimate) and are written as those doubles; wide_fields use all 64
+    bits (the HyperLogLog register checksum) and are written as two columns, <field>_hi and <field>_lo, of 32 bits
+    each; the other columns are integers (exact in float64 below 2^53).  A group over its share of DUMP_BUDGET keeps
+    a fixed sample: the rows whose splitmix64(key ^ 0x5EED) is a multiple of d, cut to the share."""
+    import numpy as np
+    from flink_amd.datagen import splitmix64
+    from flink_amd.operator import ROW_FIELDS
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BUDGET // (world * len(groups) * (len(ROW_FIELDS) + len(wide_fields)) * 8)
+    info = {}
+
+    def save(name, col):
+        np.save(os.path.join(out_dir, f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), col)
+
+    for name, rows in groups.items():
+        total = len(rows)
+        if total > cap:
+            d = -(-total // cap)
+            rows = rows[splitmix64(rows["key"].astype(np.uint64) ^ np.uint64(0x5EED)) % np.uint64(d) == 0]
+        rows = rows[np.lexsort((rows["start"], rows["key"]))][:cap]
+        for f in ROW_FIELDS:
+            col = np.ascontiguousarray(rows[f])
+            if f in wide_fields:
+                save(f"{name}_{f}_hi", (col >> 32).astype(np.float64))
+                save(f"{name}_{f}_lo", (col & 0xFFFFFFFF).astype(np.float64))
+            else:
+                save(f"{name}_{f}", col.view(np.float64) if f in f64_fields else col.astype(np.float64))
+        info[name] = {"rows": total, "rows_written": len(rows)}
+    return info
 
 
 def count_window_leg(args, batches, device):

@@ -23,7 +23,7 @@ for w in ${WORKLOADS:-c2}; do
     (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$d/prof_$mode" -o run --output-format csv \
         -- python3 "$R/bench.py" $ba --no-profile $extra > "$d/prof_$mode.log" 2>&1) || { echo "$w prof $mode rc=$?"; tail -5 "$d/prof_$mode.log"; exit 1; }
   done
-  timeout -k 10 400 python3 -u bench.py $ba --traffic "$d/traffic_${ROUND:-r06}_$w.json" > "$d/bench.json" 2> "$d/bench.err" || { echo "$w bench rc=$?"; tail -5 "$d/bench.err"; exit 1; }
+  timeout -k 10 400 python3 -u bench.py $ba --full --traffic "$d/traffic_${ROUND:-r06}_$w.json" > "$d/bench.json" 2> "$d/bench.err" || { echo "$w bench rc=$?"; tail -5 "$d/bench.err"; exit 1; }
   python3 tools/roofline_check.py "$d/bench.json" --async-trace "$d/prof_async/run_kernel_trace.csv" \
       --sync-trace "$d/prof_sync/run_kernel_trace.csv" --steps $S --warmup $W --out "$d/roofline_check.json" > /dev/null || exit 1
   python3 - "$d" <<'PY'
