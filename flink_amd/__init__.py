@@ -7,7 +7,8 @@ reference's operator interface for that path; see DESIGN.md and INTEGRATION.md.
 from .keygroups import (KeyGroupRange, assign_key_to_parallel_operator, assign_to_key_group,  # noqa: F401
                         compute_default_max_parallelism, compute_key_group_range_for_operator_index,
                         compute_operator_index_for_key_group, long_hash_code, murmur_hash, string_hash_code)
-from .windowing import (CountEvictor, CountTrigger, DeltaEvictor, GlobalWindows, TimeEvictor,  # noqa: F401
+from .windowing import (ContinuousEventTimeTrigger, CountEvictor, CountTrigger, DeltaEvictor, GlobalWindows,  # noqa: F401
+                        TimeEvictor,
                         CountSumMinMax, CountWindows, ExtremalElementReduce, FirstElementReduce, HyperLogLog, TDigest,  # noqa: F401
                         RowAggregate,
                         EventTimeSessionWindows, EventTimeTrigger, PurgingTrigger, SlidingEventTimeWindows, Time,

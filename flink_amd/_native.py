@@ -95,7 +95,7 @@ class FwWireStats(ctypes.Structure):
 
 
 FW_GLOBAL = 4
-FW_TRIGGER_EVENT_TIME, FW_TRIGGER_COUNT = 0, 1
+FW_TRIGGER_EVENT_TIME, FW_TRIGGER_COUNT, FW_TRIGGER_CONTINUOUS_EVENT_TIME = 0, 1, 2
 FW_EVICT_NONE, FW_EVICT_COUNT, FW_EVICT_TIME, FW_EVICT_DELTA = 0, 1, 2, 3
 
 
@@ -105,7 +105,8 @@ class FwListConfig(ctypes.Structure):
         "emit_contents", "max_parallelism", "key_group_start", "key_group_end", "device", "pad0")] + \
         [(n, ctypes.c_int64) for n in ("size", "slide", "offset", "allowed_lateness", "trigger_count",
                                        "evict_count")] + \
-        [("delta_threshold", ctypes.c_double), ("expected_elements", ctypes.c_int64), ("max_batch", ctypes.c_int64)]
+        [("delta_threshold", ctypes.c_double), ("expected_elements", ctypes.c_int64), ("max_batch", ctypes.c_int64),
+         ("trigger_interval", ctypes.c_int64)]
 
 
 class FwListRows(ctypes.Structure):

@@ -21,6 +21,8 @@
 // thread per list, exactly as processElement's trigger / evictor / emit sequence.  A watermark marks the
 // groups whose trigger timer (maxTimestamp) or cleanup timer is due, walks the lists of the firing ones the
 // same way, and drops the cleaned-up ones.
+// ContinuousEventTimeTrigger (triggers/ContinuousEventTimeTrigger.java:39-151) adds a fire time per group (gfire) and
+// a second timer: a watermark then fires a list once per due timer ("ContinuousEventTimeTrigger" below).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,7 +47,9 @@ constexpr int64_t LMIN = INT64_MIN;
 #ifndef FW_LIST_ROOM
 #define FW_LIST_ROOM (int64_t(1) << 28)  // elements a walk may size its output for up front
 #endif
-enum : uint32_t { GF_TIMER = 1u, GF_TOUCH = 2u, GF_FIRE = 4u, GF_CLEAN = 8u };
+// GF_FPEND: ContinuousEventTimeTrigger's timer at the window's fire time is registered
+enum : uint32_t { GF_TIMER = 1u, GF_TOUCH = 2u, GF_FIRE = 4u, GF_CLEAN = 8u, GF_FPEND = 16u };
+constexpr unsigned long long CF_MAX_FIRINGS = 1ull << 20;  // of one window in one watermark advance
 enum : uint32_t { LF_NO_TS = 1u, LF_KEY_GROUP = 2u, LF_MAP_FULL = 4u, LF_ELEMS = 8u, LF_MERGE_LATE = 16u, LF_MERGE_WIDE = 32u };
 constexpr uint32_t G_EMPTY = 0u, G_BUSY = 1u, G_LIVE = 2u, G_TOMB = 3u;
 
@@ -53,12 +57,15 @@ struct LCfg {
   int32_t assigner, vt, key_kind, trigger, purging, evictor, evict_after, side_output, emit, max_par, kg0, nkg;
   int64_t size, slide, offset, lateness, trig_n, ev_n;
   double thr;
+  int64_t trig_i;  // ContinuousEventTimeTrigger's interval
 };
 
 struct LCounters {
   unsigned long long rows, elems, side, late, dead, live_groups, tombs, nfire, nclean, count;
   unsigned int flags, need_seq;
   long long next_due;  // no group's trigger or cleanup timer is earlier: a watermark below it has nothing to do
+  // ContinuousEventTimeTrigger: the most firings one window can have in this advance, and all windows' together
+  unsigned long long maxk, rows_due;
 };
 
 struct alignas(32) GSlot {
@@ -76,6 +83,10 @@ struct alignas(32) LPay {
 struct LState {
   GSlot* g;  // the group map: one 32-byte slot per group (a lookup reads one sector)
   uint32_t gmask;
+  // ContinuousEventTimeTrigger only (null otherwise): per slot the trigger's "fire-time" state (LMIN = null), and
+  // for the time / global windows a scratch (all ones between pushes) for the first arming element of a push
+  int64_t* gfire;
+  uint32_t* gfpos;
   // session windows (FW_SESSION, fw_list.hip "session windows"): per slot its window end and list head / tail
   int64_t *wend, *whead, *wtail;
   LPay* lpay;  // the elements' payload, one 32-byte sector each (a gather reads one sector per element)
@@ -262,7 +273,7 @@ __global__ __launch_bounds__(256) void k_lp_append(LCfg c, LState S, const int64
       return;
     }
     const int64_t mts = w_max_ts(c, s);
-    due = min(due, (long long)(c.trigger == FW_TRIGGER_EVENT_TIME && mts > wm ? mts : w_cleanup(c, s)));
+    due = min(due, (long long)(c.trigger != FW_TRIGGER_COUNT && mts > wm ? mts : w_cleanup(c, s)));
     if (c.trigger == FW_TRIGGER_COUNT || mts <= wm) {  // CountTrigger / late firing
       atomicOr(&S.g[g].fl, GF_TOUCH);
       seq = true;
@@ -759,6 +770,190 @@ __global__ __launch_bounds__(256) void k_lw_clean_map(LState S) {
   block_add(&S.ctr->live_groups, (unsigned long long)(-(long long)nt));  // (wraps: a subtraction)
 }
 
+// ---------------------------------------------------------------- ContinuousEventTimeTrigger
+// ContinuousEventTimeTrigger.java:53-92 under WindowOperator.onEventTime (WindowOperator.java:424-469, the evicting
+// operator's :241-286).  A window's trigger state is `fire` (gfire[], LMIN = null) with two registered timers at the
+// most: maxTimestamp M (GF_TIMER) and fire (GF_FPEND).  One watermark runs the window's timers t <= min(wm, cleanup)
+// in ascending time:
+//   contents == null: the timer is consumed and the trigger is not asked (so a fire timer is not re-armed);
+//   t == M: FIRE, fire untouched (fire == M: continuous firing has stopped for good);
+//   else (t == fire): FIRE, fire = t + interval, a timer there.
+// Every firing is emitWindowContents (+ PurgingTrigger's clear) over what the previous one left.
+// The earliest registered trigger timer of a window, when it is <= lim
+__device__ __forceinline__ bool cf_next(int64_t M, int64_t fire, uint32_t fl, int64_t lim, int64_t* t) {
+  bool have = false;
+  int64_t x = 0;
+  if (fl & GF_TIMER) {
+    x = M;
+    have = true;
+  }
+  if ((fl & GF_FPEND) && (!have || fire < x)) {
+    x = fire;
+    have = true;
+  }
+  *t = x;
+  return have && x <= lim;
+}
+// timer t (from cf_next) runs: its registrations are consumed; with contents the trigger fires and, at its fire time,
+// moves on by one interval (a sum past Long.MAX_VALUE registers nothing more)
+__device__ __forceinline__ void cf_on_timer(const LCfg& c, int64_t M, int64_t t, bool contents, int64_t* fire,
+                                            uint32_t* fl) {
+  if (t == M) *fl &= ~GF_TIMER;
+  const bool at_fire = (*fl & GF_FPEND) && *fire == t;
+  if (at_fire) *fl &= ~GF_FPEND;
+  if (contents && at_fire && t != M) {
+    const int64_t nx = jadd(t, c.trig_i);
+    *fire = nx;
+    if (nx > t) *fl |= GF_FPEND;
+  }
+}
+// the firings the window's due timers can bring at the most (its contents never null), in closed form: the fire
+// times fire + j * interval <= lim up to and with M if they meet it, and M itself if it is registered and not met
+__device__ __forceinline__ unsigned long long cf_kmax(const LCfg& c, int64_t M, int64_t C, int64_t fire, uint32_t fl,
+                                                      int64_t wm) {
+  const int64_t lim = min(wm, C);
+  unsigned long long k = 0;
+  bool met = false;
+  if ((fl & GF_FPEND) && fire <= lim) {
+    const unsigned long long I = (unsigned long long)c.trig_i;
+    k = ((unsigned long long)lim - (unsigned long long)fire) / I + 1;
+    if (M >= fire && M <= lim && ((unsigned long long)M - (unsigned long long)fire) % I == 0) {
+      k = ((unsigned long long)M - (unsigned long long)fire) / I + 1;
+      met = true;
+    }
+  }
+  if ((fl & GF_TIMER) && M <= lim && !met) k++;
+  if (c.purging && k > 1) k = 1;  // the first firing leaves no contents
+  return k;
+}
+__device__ __forceinline__ long long cf_due_of(int64_t M, int64_t C, int64_t fire, uint32_t fl) {
+  long long d = C;
+  if (fl & GF_TIMER) d = min(d, (long long)M);
+  if (fl & GF_FPEND) d = min(d, (long long)fire);
+  return d;
+}
+
+__global__ __launch_bounds__(256) void k_fill64(int64_t* __restrict__ p, int64_t n, int64_t v) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
+}
+// push: the first element in arrival order (= log order) of every group whose fire time is null and whose window is
+// not late, then onElement's fire = ts - ts % interval + interval from that element
+__global__ __launch_bounds__(256) void k_cf_first(LCfg c, LState S, int64_t base, int64_t n, int64_t wm) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t g = S.lgid[base + i];
+    if (g < 0 || S.gfire[g] != LMIN || w_max_ts(c, S.g[g].start) <= wm) continue;
+    atomicMin(&S.gfpos[g], (uint32_t)(base + i));
+  }
+}
+__global__ __launch_bounds__(256) void k_cf_arm(LCfg c, LState S, int64_t base, int64_t n) {
+  long long due = LMAX;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t g = S.lgid[base + i];
+    if (g < 0 || S.gfpos[g] != (uint32_t)(base + i)) continue;
+    const int64_t ts = S.lpay[base + i].ts;
+    const int64_t fire = jadd(jsub(ts, ts % c.trig_i), c.trig_i);
+    S.gfire[g] = fire;
+    atomicOr(&S.g[g].fl, GF_FPEND);
+    S.gfpos[g] = 0xffffffffu;
+    due = min(due, (long long)fire);
+  }
+  block_min(&S.ctr->next_due, due);
+}
+// watermark, first pass (mark = false, nothing written but the counters): the windows with a due trigger timer, the
+// rows they can fire, the most of one window, the windows to clean up; second pass (mark = true): GF_FIRE / GF_CLEAN
+__global__ __launch_bounds__(256) void k_cf_due(LCfg c, LState S, int64_t wm, bool mark) {
+  unsigned long long nf = 0, nc = 0, rows = 0, mk = 0;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= (int64_t)S.gmask;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    if (S.g[g].st != G_LIVE) continue;
+    const int64_t st = S.g[g].start, cl = w_cleanup(c, st);
+    const uint32_t f0 = S.g[g].fl;
+    const unsigned long long k = cf_kmax(c, w_max_ts(c, st), cl, S.gfire[g], f0, wm);
+    const bool clean = cl != LMAX && cl <= wm;
+    nf += k > 0;
+    rows += k;
+    mk = max(mk, k);
+    nc += clean;
+    if (mark && (k > 0 || clean)) S.g[g].fl = f0 | (k > 0 ? GF_FIRE : 0u) | (clean ? GF_CLEAN : 0u);
+  }
+  if (mark) return;
+  block_add(&S.ctr->nfire, nf);
+  block_add(&S.ctr->nclean, nc);
+  block_add(&S.ctr->rows_due, rows);
+  if (mk) atomicMax(&S.ctr->maxk, mk);
+}
+__global__ __launch_bounds__(256) void k_walk_bound_cf(LCfg c, LState S, const uint32_t* __restrict__ keys,
+                                                       const uint32_t* __restrict__ seg, int64_t nseg, int64_t wm) {
+  unsigned long long tot = 0;
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nseg; s += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t a = seg[s], b = seg[s + 1];
+    const uint32_t g = keys[a];
+    const int64_t st = S.g[g].start;
+    tot += cf_kmax(c, w_max_ts(c, st), w_cleanup(c, st), S.gfire[g], S.g[g].fl, wm) * (unsigned long long)(b - a);
+  }
+  if (tot) atomicAdd(&S.ctr->count, tot);
+}
+// One thread per due list: its timers in ascending time.  A launch that stops at a full element buffer leaves the
+// window's trigger state as before the timer it stopped at, so the next launch goes on from there.
+__global__ __launch_bounds__(256) void k_walk_cf(LCfg c, LState S, LView V, const uint32_t* __restrict__ keys,
+                                                 const uint32_t* __restrict__ seg, int64_t nseg, int64_t wm, bool room) {
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nseg; s += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t a = seg[s], b = seg[s + 1];
+    const uint32_t g = keys[a];
+    uint32_t fl = S.g[g].fl;
+    if (!(fl & GF_FIRE)) continue;
+    const int64_t st = S.g[g].start, M = w_max_ts(c, st), lim = min(wm, w_cleanup(c, st));
+    int64_t fire = S.gfire[g], t = 0, live = 0;
+    for (int64_t q = a; q < b; q++) live += V.alive[q];
+    bool stopped = false;
+    while (cf_next(M, fire, fl, lim, &t)) {
+      const bool contents = live > 0;
+      if (contents) {
+        if (!emit_firing(c, S, V, g, a, b - 1, room)) {
+          stopped = true;
+          break;
+        }
+        if (c.purging) purge(S, V, a, b - 1);
+        if (c.purging || c.evictor != FW_EVICT_NONE) {
+          live = 0;
+          for (int64_t q = a; q < b; q++) live += V.alive[q];
+        }
+      }
+      cf_on_timer(c, M, t, contents, &fire, &fl);
+    }
+    S.gfire[g] = fire;
+    S.g[g].fl = stopped ? fl : fl & ~GF_FIRE;
+  }
+}
+// after the walk: a window still marked GF_FIRE has no contents (its due timers are consumed, the trigger not
+// asked); the cleaned-up windows become tombstones (clearAllState: the trigger's clear() drops its state); the
+// others' earliest timers
+__global__ __launch_bounds__(256) void k_cf_finish(LCfg c, LState S, int64_t wm) {
+  unsigned long long nt = 0;
+  long long due = LMAX;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= (int64_t)S.gmask;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    if (S.g[g].st != G_LIVE) continue;
+    const int64_t st = S.g[g].start, M = w_max_ts(c, st), cl = w_cleanup(c, st);
+    uint32_t fl = S.g[g].fl;
+    int64_t fire = S.gfire[g], t = 0;
+    if (fl & GF_CLEAN) {
+      S.g[g].st = G_TOMB;
+      S.gfire[g] = LMIN;
+      nt++;
+      continue;
+    }
+    if (fl & GF_FIRE) {
+      while (cf_next(M, fire, fl, min(wm, cl), &t)) cf_on_timer(c, M, t, false, &fire, &fl);
+      S.g[g].fl = fl &= ~GF_FIRE;
+    }
+    due = min(due, cf_due_of(M, cl, fire, fl));
+  }
+  block_min(&S.ctr->next_due, due);
+  block_add(&S.ctr->tombs, nt);
+  block_add(&S.ctr->live_groups, (unsigned long long)(-(long long)nt));  // (wraps: a subtraction)
+}
+
 // ---------------------------------------------------------------- compaction / rebuild
 __global__ __launch_bounds__(256) void k_rebuild_map(LCfg c, LState o, LState S, int32_t* __restrict__ remap) {
   unsigned ins = 0;
@@ -775,6 +970,7 @@ __global__ __launch_bounds__(256) void k_rebuild_map(LCfg c, LState o, LState S,
     if (ng >= 0) {
       S.g[ng].cnt = o.g[g].cnt;
       S.g[ng].fl = o.g[g].fl;
+      if (o.gfire) S.gfire[ng] = o.gfire[g];
     }
   }
   block_add(&S.ctr->live_groups, ins);
@@ -811,7 +1007,12 @@ __global__ __launch_bounds__(256) void k_count_state(LCfg c, LState S, const uin
     const int64_t cl = w_cleanup(c, S.g[g].start);
     const bool creg = event_time(c) && cl != LMAX;
     timers += creg ? 1 : 0;
-    if ((S.g[g].fl & GF_TIMER) && !(creg && cl == w_max_ts(c, S.g[g].start))) timers++;
+    const bool mreg = (S.g[g].fl & GF_TIMER) != 0;
+    if (mreg && !(creg && cl == w_max_ts(c, S.g[g].start))) timers++;
+    if (S.gfire && (S.g[g].fl & GF_FPEND)) {  // ContinuousEventTimeTrigger's timer at the fire time, if another one
+      const int64_t fire = S.gfire[g];
+      if (!(creg && cl == fire) && !(mreg && w_max_ts(c, S.g[g].start) == fire)) timers++;
+    }
   }
   if (lists) atomicAdd(&out2[0], lists);
   if (timers) atomicAdd(&out2[1], timers);
@@ -837,6 +1038,12 @@ __global__ void k_restore_groups(LCfg c, LState S, const int64_t* __restrict__ k
     if (ins) atomicAdd(&S.ctr->live_groups, 1ull);  // (one thread)
     gid_out[i] = g;
     if (g < 0) continue;
+    if (S.gfire) {  // ContinuousEventTimeTrigger: the count column is the fire time, timer its two registrations
+      if (cnt[i] != LMIN) S.gfire[g] = S.gfire[g] == LMIN ? cnt[i] : min(S.gfire[g], cnt[i]);
+      atomicOr(&S.g[g].fl, ((timer[i] & 1) ? GF_TIMER : 0u) | ((timer[i] & 2) && cnt[i] != LMIN ? GF_FPEND : 0u));
+      atomicMin(&S.ctr->next_due, cf_due_of(w_max_ts(c, start[i]), w_cleanup(c, start[i]), S.gfire[g], S.g[g].fl));
+      continue;
+    }
     S.g[g].cnt = cnt[i];
     if (timer[i]) atomicOr(&S.g[g].fl, GF_TIMER);
     atomicMin(&S.ctr->next_due, (long long)(timer[i] ? w_max_ts(c, start[i]) : w_cleanup(c, start[i])));
@@ -903,6 +1110,7 @@ __device__ int32_t sl_insert(const LState& S, int64_t key, int32_t kg, int64_t s
     S.wend[s] = end;
     S.whead[s] = -1;
     S.wtail[s] = -1;
+    if (S.gfire) S.gfire[s] = LMIN;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __hip_atomic_store(&S.g[s].st, (uint32_t)G_LIVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (cur == G_TOMB) atomicAdd(&S.ctr->tombs, (unsigned long long)-1ll);
@@ -1068,6 +1276,7 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
                                                     int64_t* __restrict__ prog, int32_t* __restrict__ pslot) {
   long long due = LMAX;
   unsigned long long killed = 0, late = 0, ins = 0, tombs = 0;
+  const bool cont = c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME;
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nruns; r += (int64_t)gridDim.x * blockDim.x) {
     int64_t q = prog[r];
     if (q == LMAX) continue;
@@ -1079,6 +1288,7 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
       if (!sl_emit(c, S, s, true, &killed)) continue;
       if (c.purging) sl_clear(S, s, &killed);
       due = min(due, (long long)sl_timer_of(c, S.g[s].fl, S.wend[s]));
+      if (cont && (S.g[s].fl & GF_FPEND)) due = min(due, (long long)S.gfire[s]);
       q++;
     } else {
       q = base + a;
@@ -1207,6 +1417,10 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
               S.wtail[target] = S.wtail[sl];
               S.g[target].cnt += S.g[sl].cnt;
             }
+            if (cont && S.gfire[sl] != LMIN) {  // the "fire-time" ReducingState merges by Min
+              S.gfire[target] = S.gfire[target] == LMIN ? S.gfire[sl] : min(S.gfire[target], S.gfire[sl]);
+              S.gfire[sl] = LMIN;
+            }
             __hip_atomic_store(&S.g[sl].st, (uint32_t)G_TOMB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             tombs++;
           }
@@ -1214,7 +1428,11 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
           for (int i = 0; i < n; i++) lo = min(lo, ms[i]);
           S.g[target].start = lo;
           S.wend[target] = ce;
-          S.g[target].fl |= GF_TIMER;  // EventTimeTrigger.onMerge registers the merged window's maxTimestamp
+          if (cont)  // ContinuousEventTimeTrigger.onMerge registers the merged fire time only; the merged windows'
+                     // own timers belong to windows that are gone (WindowOperator.onEventTime ignores them)
+            S.g[target].fl = (S.g[target].fl & ~(GF_TIMER | GF_FPEND)) | (S.gfire[target] != LMIN ? GF_FPEND : 0u);
+          else
+            S.g[target].fl |= GF_TIMER;  // EventTimeTrigger.onMerge registers the merged window's maxTimestamp
           actual = target;
         }
       }
@@ -1235,8 +1453,13 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
         if (c.purging) sl_clear(S, actual, &killed);
       } else {
         S.g[actual].fl |= GF_TIMER;
+        if (cont && S.gfire[actual] == LMIN) {  // ContinuousEventTimeTrigger.onElement: the first fire time
+          S.gfire[actual] = jadd(jsub(e.ts, e.ts % c.trig_i), c.trig_i);
+          S.g[actual].fl |= GF_FPEND;
+        }
       }
       due = min(due, (long long)sl_timer_of(c, S.g[actual].fl, S.wend[actual]));
+      if (cont && (S.g[actual].fl & GF_FPEND)) due = min(due, (long long)S.gfire[actual]);
     }
     if (q >= base + b) prog[r] = LMAX;
   }
@@ -1304,6 +1527,63 @@ __global__ __launch_bounds__(256) void k_sl_fire(LCfg c, LState S) {
   block_add(&S.ctr->live_groups, (unsigned long long)(-(long long)nt));
 }
 
+// ContinuousEventTimeTrigger over sessions.  First pass (nothing written but the counters): the rows and elements the
+// due timers can fire at the most, the most firings of one window
+__global__ __launch_bounds__(256) void k_sl_cf_due(LCfg c, LState S, int64_t wm) {
+  unsigned long long nf = 0, nc = 0, rows = 0, ne = 0, mk = 0;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= (int64_t)S.gmask;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    if (S.g[g].st != G_LIVE) continue;
+    const int64_t end = S.wend[g], cl = sl_cleanup(c, end);
+    const unsigned long long k = cf_kmax(c, sl_max_ts(end), cl, S.gfire[g], S.g[g].fl, wm);
+    nf += k > 0;
+    rows += k;
+    ne += k * (unsigned long long)S.g[g].cnt;
+    mk = max(mk, k);
+    nc += cl != LMAX && cl <= wm;
+  }
+  block_add(&S.ctr->nfire, nf);
+  block_add(&S.ctr->nclean, nc);
+  block_add(&S.ctr->count, ne);
+  block_add(&S.ctr->rows_due, rows);
+  if (mk) atomicMax(&S.ctr->maxk, mk);
+}
+// second pass: every window's due timers in ascending time (the rows and elements were sized by the host), the
+// cleanup, and the remaining windows' earliest timers
+__global__ __launch_bounds__(256) void k_sl_cf_fire(LCfg c, LState S, int64_t wm) {
+  unsigned long long killed = 0, nt = 0;
+  long long due = LMAX;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= (int64_t)S.gmask;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    if (S.g[g].st != G_LIVE) continue;
+    const int64_t end = S.wend[g], M = sl_max_ts(end), cl = sl_cleanup(c, end);
+    uint32_t fl = S.g[g].fl;
+    int64_t fire = S.gfire[g], t = 0;
+    while (cf_next(M, fire, fl, min(wm, cl), &t)) {
+      const bool contents = S.g[g].cnt > 0;
+      if (contents) {
+        sl_emit(c, S, (int32_t)g, false, &killed);
+        if (c.purging) sl_clear(S, (int32_t)g, &killed);
+      }
+      cf_on_timer(c, M, t, contents, &fire, &fl);
+    }
+    if (cl != LMAX && cl <= wm) {
+      sl_clear(S, (int32_t)g, &killed);
+      S.gfire[g] = LMIN;
+      S.g[g].st = G_TOMB;
+      nt++;
+      continue;
+    }
+    S.gfire[g] = fire;
+    S.g[g].fl = fl;
+    due = min(due, cf_due_of(M, cl, fire, fl));
+  }
+  block_min(&S.ctr->next_due, due);
+  block_add(&S.ctr->dead, killed);
+  block_add(&S.ctr->tombs, nt);
+  block_add(&S.ctr->live_groups, (unsigned long long)(-(long long)nt));
+}
+
 // compaction: the live elements' new positions, the log gathered with its links remapped, the lists' ends remapped
 __global__ __launch_bounds__(256) void k_sl_remap_set(const uint32_t* __restrict__ sel, int64_t m,
                                                       int64_t* __restrict__ remap) {
@@ -1330,6 +1610,7 @@ __global__ __launch_bounds__(256) void k_sl_rebuild(LState o, LState S, const in
     if (s < 0) continue;
     S.g[s].fl = o.g[g].fl;
     S.g[s].cnt = o.g[g].cnt;
+    if (o.gfire) S.gfire[s] = o.gfire[g];
     const int64_t h = o.whead[g], t = o.wtail[g];
     S.whead[s] = h >= 0 && remap ? remap[h] : h;
     S.wtail[s] = t >= 0 && remap ? remap[t] : t;
@@ -1347,7 +1628,10 @@ __global__ __launch_bounds__(256) void k_sl_count_state(LCfg c, LState S, unsign
     lists += S.g[g].cnt > 0;
     const int64_t cl = sl_cleanup(c, S.wend[g]);
     timers += cl != LMAX;
-    if ((S.g[g].fl & GF_TIMER) && !(cl != LMAX && cl == sl_max_ts(S.wend[g]))) timers++;
+    const bool mreg = (S.g[g].fl & GF_TIMER) != 0;
+    if (mreg && !(cl != LMAX && cl == sl_max_ts(S.wend[g]))) timers++;
+    // ContinuousEventTimeTrigger: the live windows' own fire timers (the timers of merged windows are not kept)
+    if (S.gfire && (S.g[g].fl & GF_FPEND) && S.gfire[g] != cl && !(mreg && S.gfire[g] == sl_max_ts(S.wend[g]))) timers++;
   }
   if (lists) atomicAdd(&out2[0], lists);
   if (timers) atomicAdd(&out2[1], timers);
@@ -1435,10 +1719,22 @@ int alloc_map(fw_list* op, LState& S, int64_t cap) {
   LHIP(op, dmalloc(&S.g, (size_t)cap));
   LHIP(op, hipMemsetAsync(S.g, 0, (size_t)cap * sizeof(GSlot), op->stream));  // G_EMPTY
   S.gmask = (uint32_t)(cap - 1);
+  S.gfire = nullptr;
+  S.gfpos = nullptr;
+  if (op->c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME) {  // every slot's fire time null
+    LHIP(op, dmalloc(&S.gfire, (size_t)cap));
+    hipLaunchKernelGGL(k_fill64, dim3(grid_for(cap)), dim3(256), 0, op->stream, S.gfire, cap, LMIN);
+    if (op->c.assigner != FW_SESSION) {
+      LHIP(op, dmalloc(&S.gfpos, (size_t)cap));
+      LHIP(op, hipMemsetAsync(S.gfpos, 0xff, (size_t)cap * 4, op->stream));
+    }
+  }
   return FW_OK;
 }
 void free_map(LState& S) {
   dfree(S.g);
+  dfree(S.gfire);
+  dfree(S.gfpos);
 }
 int alloc_log(fw_list* op, LState& S, int64_t cap) {
   LHIP(op, dmalloc(&S.lpay, (size_t)cap));
@@ -1559,11 +1855,17 @@ int walk_lists(fw_list* op, uint32_t bit, int64_t base_new) {
 
   // with room for every possible firing the walk reserves elements with plain atomics; else (a bound beyond
   // FW_LIST_ROOM elements) it reserves with compare-and-swap and stops where the buffer is full
+  // a ContinuousEventTimeTrigger watermark: a list fires once per due timer (k_walk_cf)
+  const bool cf = !PUSH && op->c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME;
   bool room = !op->c.emit;
   if (op->c.emit) {
     LHIP(op, hipMemsetAsync(&op->S.ctr->count, 0, 8, op->stream));
-    hipLaunchKernelGGL(k_walk_bound<PUSH>, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, op->sel2,
-                       op->keys2, op->seg, nseg, base_new);
+    if (cf)
+      hipLaunchKernelGGL(k_walk_bound_cf, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, op->keys2,
+                         op->seg, nseg, op->wm);
+    else
+      hipLaunchKernelGGL(k_walk_bound<PUSH>, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, op->sel2,
+                         op->keys2, op->seg, nseg, base_new);
     LRET(read_ctr(op));
     const int64_t need = (int64_t)op->h_ctr->elems + (int64_t)op->h_ctr->count;
     if ((int64_t)op->h_ctr->count <= FW_LIST_ROOM) {
@@ -1572,7 +1874,7 @@ int walk_lists(fw_list* op, uint32_t bit, int64_t base_new) {
     }
   }
   const bool fl = op->c.vt == FW_VAL_F64 || op->c.vt == FW_VAL_F32;
-  if (!PUSH && room && op->c.emit && op->c.evictor == FW_EVICT_NONE && !fl) {  // the common apply shape
+  if (!PUSH && !cf && room && op->c.emit && op->c.evictor == FW_EVICT_NONE && !fl) {  // the common apply shape
     LRET(read_ctr(op));
     const int64_t rbase = (int64_t)op->h_ctr->rows, ebase = (int64_t)op->h_ctr->elems;
     hipLaunchKernelGGL(k_gather_emit, dim3(grid_for(m)), dim3(256), 0, op->stream, op->S, op->sel2, m, ebase);
@@ -1588,8 +1890,12 @@ int walk_lists(fw_list* op, uint32_t bit, int64_t base_new) {
   const LView V{op->sel2, op->gts, op->gval, op->gord, op->galive, op->S.lgid};
   for (int round = 0;; round++) {
     LHIP(op, hipMemsetAsync(&op->S.ctr->flags, 0, 4, op->stream));
-    hipLaunchKernelGGL(k_walk<PUSH>, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, V, op->keys2,
-                       op->seg, nseg, base_new, op->wm, op->prog, room);
+    if (cf)
+      hipLaunchKernelGGL(k_walk_cf, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, V, op->keys2, op->seg,
+                         nseg, op->wm, room);
+    else
+      hipLaunchKernelGGL(k_walk<PUSH>, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, V, op->keys2,
+                         op->seg, nseg, base_new, op->wm, op->prog, room);
     LHIP(op, hipGetLastError());
     LRET(read_ctr(op));
     if (!(op->h_ctr->flags & LF_ELEMS)) break;
@@ -1815,6 +2121,42 @@ int sl_watermark(fw_list* op, int64_t wm) {
   return sl_maybe_compact(op);
 }
 
+// processWatermark under ContinuousEventTimeTrigger: a first pass over the windows counts what their due timers can
+// fire (nothing is changed before the 2^20 limit is checked), then they fire timer by timer
+int cf_watermark(fw_list* op, int64_t wm) {
+  LHIP(op, hipMemsetAsync(&op->S.ctr->nfire, 0, 24, op->stream));  // nfire, nclean, count
+  LHIP(op, hipMemsetAsync(&op->S.ctr->maxk, 0, 16, op->stream));   // maxk, rows_due
+  if (sessions(op))
+    hipLaunchKernelGGL(k_sl_cf_due, dim3(grid_for(op->gcap)), dim3(256), 0, op->stream, op->c, op->S, wm);
+  else
+    hipLaunchKernelGGL(k_cf_due, dim3(grid_for(op->gcap)), dim3(256), 0, op->stream, op->c, op->S, wm, false);
+  LHIP(op, hipGetLastError());
+  LRET(read_ctr(op));
+  if (op->h_ctr->maxk > CF_MAX_FIRINGS)
+    return set_err(op, FW_ERR_UNSUPPORTED, "watermark advance crosses more than 2^20 trigger intervals of a window");
+  const int64_t nfire = (int64_t)op->h_ctr->nfire, nclean = (int64_t)op->h_ctr->nclean;
+  const int64_t rows = (int64_t)op->h_ctr->rows_due, elems = (int64_t)op->h_ctr->count;
+  op->wm = wm;
+  const long long none = LMAX;
+  LHIP(op, hipMemcpyAsync(&op->S.ctr->next_due, &none, 8, hipMemcpyHostToDevice, op->stream));
+  LRET(ensure_rows(op, (int64_t)op->h_ctr->rows + rows));
+  if (sessions(op)) {
+    if (op->c.emit) LRET(ensure_elems(op, (int64_t)op->h_ctr->elems + elems));
+    hipLaunchKernelGGL(k_sl_cf_fire, dim3(grid_for(op->gcap)), dim3(256), 0, op->stream, op->c, op->S, wm);
+    LHIP(op, hipGetLastError());
+    LRET(read_ctr(op));
+    return sl_maybe_compact(op);
+  }
+  if (nfire || nclean)
+    hipLaunchKernelGGL(k_cf_due, dim3(grid_for(op->gcap)), dim3(256), 0, op->stream, op->c, op->S, wm, true);
+  if (nfire) LRET(walk_lists<false>(op, GF_FIRE, 0));
+  if (nclean) hipLaunchKernelGGL(k_lw_clean_log, dim3(grid_for(op->n_log)), dim3(256), 0, op->stream, op->S, op->n_log);
+  hipLaunchKernelGGL(k_cf_finish, dim3(grid_for(op->gcap)), dim3(256), 0, op->stream, op->c, op->S, wm);
+  LHIP(op, hipGetLastError());
+  LRET(read_ctr(op));
+  return maybe_compact(op);
+}
+
 int push_device(fw_list* op, const int64_t* key, const int64_t* ts, const int64_t* val, const int32_t* kh, int64_t n) {
   if (n == 0) return FW_OK;
   if (n > op->max_batch) return set_err(op, FW_ERR_ARG, "batch of %lld records exceeds max_batch %lld", (long long)n,
@@ -1869,6 +2211,11 @@ int push_device(fw_list* op, const int64_t* key, const int64_t* ts, const int64_
   op->n_log += E;
   op->ord_base += n;
   op->records_in += n;
+  if (op->c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME && E) {  // onElement arms the groups without a fire time
+    hipLaunchKernelGGL(k_cf_first, dim3(grid_for(E)), dim3(256), 0, op->stream, op->c, op->S, base, E, op->wm);
+    hipLaunchKernelGGL(k_cf_arm, dim3(grid_for(E)), dim3(256), 0, op->stream, op->c, op->S, base, E);
+    LHIP(op, hipGetLastError());
+  }
   // (the counters are current: read after the last append)
   if (op->h_ctr->need_seq) {
     LRET(walk_lists<true>(op, GF_TOUCH, base));
@@ -1896,15 +2243,18 @@ int fw_list_create(const fw_list_config* cfg, fw_list** out) {
     return fail(FW_ERR_UNSUPPORTED, "assigner must be FW_TUMBLING, FW_SLIDING, FW_SESSION or FW_GLOBAL");
   if (c.assigner == FW_SESSION && c.size <= 0)
     return fail(FW_ERR_ARG, "EventTimeSessionWindows parameters must satisfy 0 < size");
-  if (c.assigner == FW_SESSION && c.trigger != FW_TRIGGER_EVENT_TIME)
-    return fail(FW_ERR_UNSUPPORTED, "session windows over ListState are offered with EventTimeTrigger (or PurgingTrigger "
-                                    "of it)");
+  if (c.assigner == FW_SESSION && c.trigger != FW_TRIGGER_EVENT_TIME && c.trigger != FW_TRIGGER_CONTINUOUS_EVENT_TIME)
+    return fail(FW_ERR_UNSUPPORTED, "session windows over ListState are offered with EventTimeTrigger or "
+                                    "ContinuousEventTimeTrigger (or PurgingTrigger of either)");
   if (c.assigner == FW_TUMBLING && (c.size <= 0 || c.offset < 0 || c.offset >= c.size))
     return fail(FW_ERR_ARG, "TumblingEventTimeWindows parameters must satisfy 0 <= offset < size");
   if (c.assigner == FW_SLIDING && (c.size <= 0 || c.slide <= 0 || c.slide > c.size || c.offset < 0 || c.offset >= c.slide))
     return fail(FW_ERR_ARG, "SlidingEventTimeWindows parameters must satisfy 0 <= offset < slide <= size");
   if (c.allowed_lateness < 0) return fail(FW_ERR_ARG, "The allowed lateness cannot be negative.");
-  if (c.trigger != FW_TRIGGER_EVENT_TIME && c.trigger != FW_TRIGGER_COUNT) return fail(FW_ERR_ARG, "unknown trigger");
+  if (c.trigger != FW_TRIGGER_EVENT_TIME && c.trigger != FW_TRIGGER_COUNT && c.trigger != FW_TRIGGER_CONTINUOUS_EVENT_TIME)
+    return fail(FW_ERR_ARG, "unknown trigger");
+  if (c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME && c.trigger_interval <= 0)
+    return fail(FW_ERR_ARG, "ContinuousEventTimeTrigger interval must be > 0");
   if (c.trigger == FW_TRIGGER_COUNT && (c.trigger_count <= 0 || c.trigger_count > INT32_MAX))
     return fail(FW_ERR_ARG, "CountTrigger count must be in [1, 2^31)");
   if (c.evictor < FW_EVICT_NONE || c.evictor > FW_EVICT_DELTA) return fail(FW_ERR_ARG, "unknown evictor");
@@ -1917,7 +2267,8 @@ int fw_list_create(const fw_list_config* cfg, fw_list** out) {
   if (mp <= 0 || mp > 32768 || kg0 > kg1 || kg1 >= mp) return fail(FW_ERR_ARG, "invalid KeyGroupRange");
   op->c = LCfg{c.assigner, c.value_type, c.key_kind, c.trigger, c.purging, c.evictor, c.evict_after, c.side_output,
                c.emit_contents, mp, kg0, kg1 - kg0 + 1, c.size, c.slide, c.offset, c.allowed_lateness,
-               c.trigger_count, c.evict_count, c.delta_threshold};
+               c.trigger_count, c.evict_count, c.delta_threshold,
+               c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME ? c.trigger_interval : 0};
   op->device = c.device;
   if (hipSetDevice(c.device) != hipSuccess) return fail(FW_ERR_HIP, "hipSetDevice failed");
   if (hipStreamCreateWithFlags(&op->stream, hipStreamNonBlocking) != hipSuccess)
@@ -2036,6 +2387,8 @@ int fw_list_advance_watermark(fw_list* op, int64_t wm, int64_t* n_pending_rows) 
   LRET(read_ctr(op));
   if (wm > op->wm && wm < op->h_ctr->next_due) {
     op->wm = wm;  // no timer is due
+  } else if (wm > op->wm && op->c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME) {
+    LRET(cf_watermark(op, wm));
   } else if (wm > op->wm) {  // HeapInternalTimerService.advanceWatermark: timers <= wm, in any order across lists
     op->wm = wm;
     const long long none = LMAX;
@@ -2220,6 +2573,17 @@ int fw_list_snapshot_key_group(fw_list* op, int32_t key_group, const fw_list_sta
     LHIP(op, hipMemcpy(&gs, op->S.g + g, sizeof gs, hipMemcpyDeviceToHost));
     const int64_t key = gs.key, start = gs.start, c = gs.cnt;
     const uint32_t fl = gs.fl;
+    if (op->S.gfire) {  // ContinuousEventTimeTrigger: the fire time and the two timers' registrations
+      int64_t fire = LMIN;
+      LHIP(op, hipMemcpy(&fire, op->S.gfire + g, 8, hipMemcpyDeviceToHost));
+      dst->key[i] = key;
+      dst->start[i] = start;
+      dst->end[i] = op->c.assigner == FW_GLOBAL ? LMAX : (int64_t)((uint64_t)start + (uint64_t)op->c.size);
+      dst->trigger_count[i] = fire;
+      dst->timer[i] = ((fl & GF_TIMER) ? 1 : 0) | ((fl & GF_FPEND) ? 2 : 0);
+      dst->n_elems[i] = cnt[i];
+      continue;
+    }
     dst->key[i] = key;
     dst->start[i] = start;
     dst->end[i] = op->c.assigner == FW_GLOBAL ? LMAX : (int64_t)((uint64_t)start + (uint64_t)op->c.size);

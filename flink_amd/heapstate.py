@@ -776,18 +776,31 @@ def trigger_counts_from_heap(count_mappings):
     return {(key, window): int(c) for window, key, c in count_mappings}
 
 
-def list_state_from_heap(mappings, timers, key_id, value_of, ts_of=None, ordinal_base=0, trigger_counts=None):
+def fire_times_from_heap(fire_mappings):
+    """ContinuousEventTimeTrigger's next early firing: its ReducingState "fire-time" (Min over LongSerializer,
+    ContinuousEventTimeTrigger.java:45-46, read with serializers (window, key, LongSer())) as {(key, window): fire}"""
+    return {(key, window): int(f) for window, key, f in fire_mappings}
+
+
+def list_state_from_heap(mappings, timers, key_id, value_of, ts_of=None, ordinal_base=0, trigger_counts=None,
+                         fire_times=None):
     """A window-contents ListState (WindowOperator: the values; EvictingWindowOperator: StreamRecords) as the list
     operator's state: (lists [dict key, start, end, trigger_count, timer, n_elems], elements [(ts, val, ordinal)]).
     Values without a timestamp get Long.MIN_VALUE ("no timestamp").  trigger_counts: a CountTrigger's counts
     (trigger_counts_from_heap); without them every window restores with count 0, which is right only for
-    EventTimeTrigger operators (the list operator refuses nothing here: the caller knows its trigger)."""
+    EventTimeTrigger operators (the list operator refuses nothing here: the caller knows its trigger).
+    fire_times: a ContinuousEventTimeTrigger's fire times (fire_times_from_heap) instead: the trigger_count column
+    then carries a window's fire time, Long.MIN_VALUE when it has none, and timer gains bit 2 when the timer at that
+    fire time is among `timers` (fw_list_state, include/flink_window.h)."""
     lists, elems = [], []
     o = ordinal_base
     for (start, end), key, values in mappings:
         tc = trigger_counts.get((key, (start, end)), 0) if trigger_counts else 0
-        lists.append(dict(key=key_id(key), start=start, end=end, trigger_count=tc,
-                          timer=int((key, (start, end), end - 1) in timers), n_elems=len(values)))
+        timer = int((key, (start, end), end - 1) in timers)
+        if fire_times is not None:
+            tc = fire_times.get((key, (start, end)), -(1 << 63))
+            timer |= 2 * int((key, (start, end), tc) in timers)
+        lists.append(dict(key=key_id(key), start=start, end=end, trigger_count=tc, timer=timer, n_elems=len(values)))
         for v in values:
             ts = ts_of(v) if ts_of else None
             elems.append((-(1 << 63) if ts is None else ts, value_of(v), o))

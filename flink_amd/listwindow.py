@@ -6,6 +6,9 @@ with an Iterable window function, and the EvictingWindowOperator (f4; include/fl
   EvictingWindowOperator(..., trigger, evictor, ...)            (EvictingWindowOperator.java:76-98)
   processElement -> process_batch, processWatermark -> process_watermark   (EvictingWindowOperator.java:102-286)
 
+Triggers: EventTimeTrigger, CountTrigger.of(n) (not over sessions), ContinuousEventTimeTrigger.of(interval) — early
+firings, possibly several of one window per watermark — each alone or inside PurgingTrigger.
+
 Every firing yields a row (key, window, count, the built-in reduce sum / min / max over the contents, the first
 element's arrival ordinal) and, with emit_contents, its elements in list order, on which `window_function(key,
 window, elements)` — the host's Iterable function — is applied.  All state lives in HBM and every call goes through
@@ -18,7 +21,8 @@ import numpy as np
 from . import _native as N
 from .keygroups import KeyGroupRange
 from .operator import _KEY_KINDS, _is_torch
-from .windowing import VALUE_TYPES, CountTrigger, EventTimeTrigger, Evictor, Trigger, WindowAssigner
+from .windowing import (VALUE_TYPES, ContinuousEventTimeTrigger, CountTrigger, EventTimeTrigger, Evictor, Trigger,
+                        WindowAssigner)
 
 LIST_ROW_FIELDS = ("key", "start", "end", "count", "sum", "min", "max", "first", "elem_off")
 LIST_ROW_DTYPE = np.dtype([(f, "<i8") for f in LIST_ROW_FIELDS] + [("epoch", "<i8")])
@@ -34,8 +38,9 @@ class GpuListWindowOperator:
                  expected_elements=0, max_batch=0):
         trigger = trigger or EventTimeTrigger.create()
         nested = getattr(trigger, "nested", trigger)
-        if not isinstance(nested, (EventTimeTrigger, CountTrigger)):
-            raise ValueError("triggers: EventTimeTrigger, CountTrigger, or PurgingTrigger of either")
+        if not isinstance(nested, (EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger)):
+            raise ValueError("triggers: EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger, or PurgingTrigger "
+                             "of one of them")
         if allowed_lateness < 0:
             raise ValueError("The allowed lateness cannot be negative.")
         kgr = key_group_range or KeyGroupRange(0, max_parallelism - 1)
@@ -47,7 +52,10 @@ class GpuListWindowOperator:
             c.size = cfg["gap"]
         c.value_type = VALUE_TYPES[value_type]
         c.key_kind = _KEY_KINDS[key_type]
-        c.trigger = N.FW_TRIGGER_COUNT if isinstance(nested, CountTrigger) else N.FW_TRIGGER_EVENT_TIME
+        c.trigger = (N.FW_TRIGGER_COUNT if isinstance(nested, CountTrigger)
+                     else N.FW_TRIGGER_CONTINUOUS_EVENT_TIME if isinstance(nested, ContinuousEventTimeTrigger)
+                     else N.FW_TRIGGER_EVENT_TIME)
+        c.trigger_interval = nested.interval if isinstance(nested, ContinuousEventTimeTrigger) else 0
         c.trigger_count = nested.count if isinstance(nested, CountTrigger) else 0
         c.purging = int(trigger.purging)
         ev = evictor or Evictor()
@@ -226,7 +234,9 @@ class GpuListWindowOperator:
 
     # ------------------------------------------------------------------ snapshot / restore per key group
     def snapshot_key_group(self, kg):
-        """(lists LIST_STATE_DTYPE, elements ELEM_DTYPE concatenated in list order) of key group kg."""
+        """(lists LIST_STATE_DTYPE, elements ELEM_DTYPE concatenated in list order) of key group kg.  Under
+        ContinuousEventTimeTrigger the trigger_count column holds the windows' fire times (Long.MIN_VALUE: none)
+        and timer the registrations of both timers (1: maxTimestamp, 2: the fire time)."""
         L = N.lib()
         nl, ne = ctypes.c_int64(), ctypes.c_int64()
         self._check(L.fw_list_snapshot_key_group(self._h, int(kg), None, 0, 0, ctypes.byref(nl), ctypes.byref(ne)))

@@ -157,13 +157,14 @@ class EventTimeTrigger(Trigger):
 
 
 class PurgingTrigger(Trigger):
-    """PurgingTrigger.of(EventTimeTrigger.create()) (PurgingTrigger.java:45-59); around CountTrigger.of(n) for the
-    window-contents operator only."""
+    """PurgingTrigger.of(EventTimeTrigger.create()) (PurgingTrigger.java:45-59); around CountTrigger.of(n) or
+    ContinuousEventTimeTrigger.of(interval) for the window-contents operator only."""
     purging = True
 
     def __init__(self, nested):
-        if not isinstance(nested, (EventTimeTrigger, CountTrigger)):
-            raise ValueError("the GPU path offers PurgingTrigger only around EventTimeTrigger or CountTrigger")
+        if not isinstance(nested, (EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger)):
+            raise ValueError("the GPU path offers PurgingTrigger only around EventTimeTrigger, CountTrigger or "
+                             "ContinuousEventTimeTrigger")
         self.nested = nested
 
     @staticmethod
@@ -198,6 +199,25 @@ class CountTrigger(Trigger):
     @staticmethod
     def of(count):
         return CountTrigger(count)
+
+
+class ContinuousEventTimeTrigger(Trigger):
+    """ContinuousEventTimeTrigger.of(Time.milliseconds(interval)) (ContinuousEventTimeTrigger.java:39-151): early
+    firings every `interval` ms of event time from the first element's interval on, and at the window's maxTimestamp;
+    for the window-contents operator (GpuListWindowOperator) over time, global and session windows."""
+
+    def __init__(self, interval):
+        interval = getattr(interval, "ms", interval)
+        if interval <= 0:
+            raise ValueError("interval must be positive")
+        self.interval = int(interval)
+
+    @staticmethod
+    def of(interval):
+        return ContinuousEventTimeTrigger(interval)
+
+    def __repr__(self):
+        return f"ContinuousEventTimeTrigger({self.interval})"
 
 
 class Evictor:

@@ -551,8 +551,14 @@ int fw_wire_encode_device(fw_wire* w, const fw_rows* rows, int64_t n, int32_t f6
  * (runtime/operators/windowing/EvictingWindowOperator.java:102-366; without an evictor WindowOperator.java:291-469):
  *   assigners  FW_TUMBLING, FW_SLIDING (every window of a record holds a copy), FW_GLOBAL (GlobalWindows: never
  *              late, never cleaned up; rows have start = Long.MIN_VALUE, end = Long.MAX_VALUE = their timestamp);
- *   triggers   FW_TRIGGER_EVENT_TIME (EventTimeTrigger.java:37-73) or FW_TRIGGER_COUNT (CountTrigger.of(n),
- *              CountTrigger.java:47-70), either wrapped in PurgingTrigger (purging = 1);
+ *   triggers   FW_TRIGGER_EVENT_TIME (EventTimeTrigger.java:37-73), FW_TRIGGER_COUNT (CountTrigger.of(n),
+ *              CountTrigger.java:47-70) or FW_TRIGGER_CONTINUOUS_EVENT_TIME (ContinuousEventTimeTrigger.of(interval),
+ *              ContinuousEventTimeTrigger.java:39-151: early firings every trigger_interval ms of event time until
+ *              the window's maxTimestamp, over time, global and session windows), each wrapped in PurgingTrigger
+ *              (purging = 1) or not.  With the continuous trigger one watermark can fire a window several times: its
+ *              due timers run in ascending time, every firing a row of its own (an evictor runs per firing; a timer
+ *              that finds no contents does not reach the trigger, so it is not re-armed: WindowOperator.java:446-459).
+ *              More than 2^20 firings of one window in one advance are refused (FW_ERR_UNSUPPORTED, nothing changed);
  *   evictors   CountEvictor.of(n[, after]) (CountEvictor.java:50-78), TimeEvictor.of(ms[, after]) (TimeEvictor.java
  *              :54-104; a timestamp of Long.MIN_VALUE is "no timestamp": nothing is evicted when the first element
  *              has none), DeltaEvictor.of(threshold, f[, after]) with the built-in f(e, last) = last.field - e.field
@@ -566,6 +572,7 @@ int fw_wire_encode_device(fw_wire* w, const fw_rows* rows, int64_t n, int32_t f6
 #define FW_GLOBAL 4
 #define FW_TRIGGER_EVENT_TIME 0
 #define FW_TRIGGER_COUNT 1
+#define FW_TRIGGER_CONTINUOUS_EVENT_TIME 2
 #define FW_EVICT_NONE 0
 #define FW_EVICT_COUNT 1
 #define FW_EVICT_TIME 2
@@ -591,6 +598,7 @@ typedef struct fw_list_config {
   double delta_threshold;    /* DeltaEvictor threshold                                            */
   int64_t expected_elements; /* sizing hint: elements held at once (0 = default)                  */
   int64_t max_batch;         /* largest n of one push (0 = 1 << 24)                               */
+  int64_t trigger_interval;  /* ContinuousEventTimeTrigger.of(interval), ms (> 0 for that trigger)      */
 } fw_list_config;
 typedef struct fw_list_rows {
   int64_t *key, *start, *end, *count, *sum, *min, *max;
@@ -602,7 +610,11 @@ typedef struct fw_list_elems {
 } fw_list_elems;
 /* A key group's list state, for snapshot / restore (the heap backend writes "window-contents" per key group:
  * HeapKeyedStateBackend.java:370-381): per (key, window) its list, CountTrigger's count and whether its
- * EventTimeTrigger timer is registered; the elements of all lists concatenated in list order. */
+ * EventTimeTrigger timer is registered; the elements of all lists concatenated in list order.
+ * With FW_TRIGGER_CONTINUOUS_EVENT_TIME the trigger_count column carries the trigger's "fire-time" state instead
+ * (the next early firing; Long.MIN_VALUE = null), and timer is a bit set: 1 = the maxTimestamp timer is registered,
+ * 2 = the timer at the fire time is registered (it is not once a firing at maxTimestamp or a timer over empty
+ * contents has consumed it). */
 typedef struct fw_list_state {
   int64_t *key, *start, *end, *trigger_count, *timer, *n_elems;  /* per list   */
   int64_t *ts, *val, *ordinal;                                   /* elements   */
@@ -617,7 +629,8 @@ int fw_list_push_batch(fw_list* op, const int64_t* key, const int64_t* ts, const
                        int64_t n);
 int fw_list_push_batch_device(fw_list* op, const int64_t* key, const int64_t* ts, const void* val,
                               const int32_t* key_hash, int64_t n);
-/* processWatermark: the EventTimeTrigger timers <= wm fire their lists, cleanup timers drop them */
+/* processWatermark: the trigger's event-time timers <= wm fire their lists (a ContinuousEventTimeTrigger window once
+ * per due timer), cleanup timers drop them */
 int fw_list_advance_watermark(fw_list* op, int64_t wm, int64_t* n_pending_rows);
 int fw_list_pending(fw_list* op, int64_t* n_rows, int64_t* n_elems, int64_t* n_side_rows);
 /* copies the pending rows (and elements: elem_off counts from the first drained element) into host arrays and

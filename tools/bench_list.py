@@ -31,13 +31,16 @@ def main():
     ap.add_argument("--rate", type=int, default=100_000_000)
     ap.add_argument("--window", type=int, default=1000)
     ap.add_argument("--evictor", default="none", help="none | count:N | time:MS")
+    ap.add_argument("--trigger", default="event_time", choices=["event_time", "continuous"],
+                    help="continuous: ContinuousEventTimeTrigger.of(--interval), early firings of every window")
+    ap.add_argument("--interval", type=int, default=250, help="ContinuousEventTimeTrigger's interval, ms")
     ap.add_argument("--cpu-sample", type=int, default=1 << 22)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     args = ap.parse_args()
 
     import numpy as np
     import torch
-    from flink_amd import CountEvictor, TimeEvictor, TumblingEventTimeWindows
+    from flink_amd import ContinuousEventTimeTrigger, CountEvictor, TimeEvictor, TumblingEventTimeWindows
     from flink_amd.datagen import generate_device
     from flink_amd.listwindow import GpuListWindowOperator
 
@@ -47,7 +50,10 @@ def main():
     elif args.evictor.startswith("time:"):
         ev = TimeEvictor.of(int(args.evictor[5:]))
     per_window = args.rate * args.window // 1000
-    op = GpuListWindowOperator(TumblingEventTimeWindows.of(args.window), evictor=ev, max_batch=args.batch,
+    trig = ContinuousEventTimeTrigger.of(args.interval) if args.trigger == "continuous" else None
+    if trig is not None:
+        args.no_cpu_baseline = True  # (the ListState oracle has no such trigger)
+    op = GpuListWindowOperator(TumblingEventTimeWindows.of(args.window), trigger=trig, evictor=ev, max_batch=args.batch,
                                expected_elements=int(per_window * 1.3))
     dev = torch.device("cuda", 0)
     batches, wms, m = [], [], -(1 << 63)
@@ -109,6 +115,7 @@ def main():
         "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "dtype": "int64",
         "data": "synthetic (splitmix64 counter stream)",
         "config": {"workload": f"f4: tumbling {args.window} ms apply over ListState, evictor {args.evictor}, "
+                               + (f"ContinuousEventTimeTrigger({args.interval} ms), " if trig is not None else "") +
                                f"{args.keys} uniform Long keys, {args.rate} records per event-second, 2^24 per step",
                    "fired_rows": fired, "fired_elements": elems, "table_grows": st["table_grows"]},
         "path_roofline": {"b_alg_bytes_per_record": B_ALG, "frac": round(B_ALG * value / 8e12, 4),
