@@ -390,9 +390,17 @@ __device__ __forceinline__ void acc_merge(const DevCfg& c, Entry& a, const Entry
   a.mn = b.mn < a.mn ? b.mn : a.mn;
   a.mx = b.mx > a.mx ? b.mx : a.mx;
 }
-__device__ __forceinline__ void acc_clear(Entry& e) {
+// the bits an accumulator's sum starts from.  The reduce aggregates (sum(pos) / max(pos) / minBy / maxBy) keep a
+// ReducingState whose first element is the state (HeapReducingState.java:72-84), so a Double / Float window of
+// -0.0 alone sums to -0.0: their sums start from -0.0, the additive identity of every double (-0.0 + x = x, and
+// -0.0 + -0.0 = -0.0 when deltas merge).  CountSumMinMax starts from createAccumulator's +0.0.  `agg`: the
+// aggregate, or lds_acc's `first` (0 / LDS_CNT_ONLY for the aggregates without ordinals)
+__host__ __device__ __forceinline__ int64_t sum_zero(int vtype, int agg) {
+  return vtype == FW_VAL_F64 && agg >= FW_AGG_FIRST && agg <= FW_AGG_FIRST_MAX ? (int64_t)0x8000000000000000ull : 0;
+}
+__device__ __forceinline__ void acc_clear(const DevCfg& c, Entry& e) {
   e.cnt = 0;
-  e.sum = 0;
+  e.sum = sum_zero(c.vtype, c.agg);
   e.mn = LMAX;
   e.mx = LMIN;
 }
@@ -1487,7 +1495,8 @@ __device__ __forceinline__ void lds_acc_delta(AggLds& L, int target, int vtype, 
 // iteration (CAS EMPTY -> BUSY, write the key, store the fingerprint), so lanes of its own wave that
 // wait on the BUSY tag see the fingerprint on their next iteration.  LDS operations of one wave
 // complete in order, so a reader that sees the fingerprint reads the key written before it.
-__device__ __forceinline__ int lds_slot(AggLds& L, int64_t key, int64_t start) {
+// (sum0: sum_zero of the operator, what a claimed slot's sum starts from)
+__device__ __forceinline__ int lds_slot(AggLds& L, int64_t key, int64_t start, int64_t sum0) {
   const uint32_t h = lds_hash(key, start), fp = lds_fp(h);
   uint32_t b = h & (LDS_BUCKETS - 1);
   int target = -1;
@@ -1531,7 +1540,7 @@ __device__ __forceinline__ int lds_slot(AggLds& L, int64_t key, int64_t start) {
       if (atomicCAS(&L.tag[s], LT_EMPTY, LT_BUSY) == LT_EMPTY) {
         L.kv[s] = i64x2{key, start};
         L.cnt[s] = 0;
-        L.sum[s] = 0;
+        L.sum[s] = sum0;
         L.mn[s] = LMAX;
         L.mx[s] = LMIN;
         __hip_atomic_store(&L.tag[s], fp, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1548,7 +1557,7 @@ __device__ __forceinline__ int lds_slot(AggLds& L, int64_t key, int64_t start) {
 }
 __device__ __forceinline__ bool lds_upsert(AggLds& L, int vtype, int64_t key, int64_t start, int64_t v,
                                            int diag = 0, int64_t fo = 0, int first = 0) {
-  const int target = lds_slot(L, key, start);
+  const int target = lds_slot(L, key, start, sum_zero(vtype, first));
   if (target < 0) return false;
   if (diag & DIAG_AGG_NO_ACCUM) return true;
   lds_acc(L, target, vtype, v, fo, first);
@@ -1634,7 +1643,7 @@ __device__ __forceinline__ bool lds_upsert_batch(AggLds& L, int vtype, const int
 #pragma unroll
   for (int j = 0; j < RPT; j++) {
     if (dm >> j & 1) continue;
-    const int target = lds_slot(L, k[j], s[j]);
+    const int target = lds_slot(L, k[j], s[j], sum_zero(vtype, first));
     if (target < 0) return false;
     lds_acc(L, target, vtype, v[j], o[j], first);
     dm |= 1u << j;
@@ -1818,7 +1827,7 @@ __device__ __forceinline__ bool agg_flush(const DevCfg& c, AggLds& L, const Regi
 // it, which is always connected) and its accumulator; `end` lives in the separate array E.  An element
 // joins a slot of its key whose interval intersects its window and widens it with LDS min/max, or
 // claims a new slot.  Slots of one key that come to overlap are joined by the flush.
-__device__ __forceinline__ int lds_session_slot(AggLds& L, int64_t* E, int64_t key, int64_t ws, int64_t we) {
+__device__ __forceinline__ int lds_session_slot(AggLds& L, int64_t* E, int64_t key, int64_t ws, int64_t we, int64_t sum0) {
   const uint32_t h = lds_hash(key, 0), fp = lds_fp(h);
   uint32_t b = h & (LDS_BUCKETS - 1);
   int target = -1;
@@ -1848,7 +1857,7 @@ __device__ __forceinline__ int lds_session_slot(AggLds& L, int64_t* E, int64_t k
         L.kv[s] = i64x2{key, ws};
         E[s] = we;
         L.cnt[s] = 0;
-        L.sum[s] = 0;
+        L.sum[s] = sum0;
         L.mn[s] = LMAX;
         L.mx[s] = LMIN;
         __hip_atomic_store(&L.tag[s], fp, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1871,7 +1880,7 @@ __device__ __forceinline__ int lds_session_slot(AggLds& L, int64_t* E, int64_t k
 }
 __device__ __forceinline__ bool lds_session_upsert(AggLds& L, int64_t* E, int vtype, int64_t key, int64_t ws,
                                                    int64_t we, int64_t v, int64_t fo = 0, int first = 0) {
-  const int target = lds_session_slot(L, E, key, ws, we);
+  const int target = lds_session_slot(L, E, key, ws, we, sum_zero(vtype, first));
   if (target < 0) return false;
   lds_acc(L, target, vtype, v, fo, first);
   return true;
@@ -2582,7 +2591,7 @@ __device__ __forceinline__ void agg_walk_lm(const DevCfg& c, AggLds& L, int64_t*
 #pragma unroll
       for (int j = 0; j < RPT; j++) {
         const bool act = up && !(m >> j & 1);
-        const int tg = act ? lds_session_slot(L, E, k[j], t[j], jadd(t[j], c.gap)) : -1;
+        const int tg = act ? lds_session_slot(L, E, k[j], t[j], jadd(t[j], c.gap), sum_zero(c.vtype, c.agg)) : -1;
         if (act && tg < 0) up = false;
         if constexpr (FIRST) {
           if (tg >= 0) lds_acc(L, tg, c.vtype, v[j], o[j], c.agg);
@@ -2710,9 +2719,9 @@ __device__ __forceinline__ void agg_split(const DevCfg& c, AggLds& L, int64_t* E
           if (failed || q < rj || rb + (int64_t)q * blockDim.x + threadIdx.x >= de) continue;
           int tg;
           if constexpr (SESS)
-            tg = lds_session_slot(L, E, d[q].key, d[q].start, d[q].end);
+            tg = lds_session_slot(L, E, d[q].key, d[q].start, d[q].end, sum_zero(c.vtype, c.agg));
           else
-            tg = lds_slot(L, d[q].key, d[q].start);
+            tg = lds_slot(L, d[q].key, d[q].start, sum_zero(c.vtype, c.agg));
           if (tg < 0) {
             failed = true;
             rj = q;
@@ -3104,7 +3113,7 @@ __device__ void replay_time_windows(const SlowCtx& x, int32_t p, int64_t k, int6
       ne.key = k;
       ne.start = s;
       ne.end = e;
-      acc_clear(ne);
+      acc_clear(c, ne);
       ne.meta = c.pool_bytes ? (int64_t)(pool_new_block(c, x.st) << 1) : 0;
       slot = new_slot(x, r, p, h, ne);
       if (slot < 0) continue;
@@ -3153,7 +3162,7 @@ __device__ void replay_time_windows(const SlowCtx& x, int32_t p, int64_t k, int6
         td_purge(c, ((uint32_t)p << c.log_r) | (uint32_t)slot, pool_block_of(en));
       else
         hll_clear(c, pool_block_of(en));
-      acc_clear(en);
+      acc_clear(c, en);
       en.meta &= ~(int64_t)FW_TIMER;
       keep = true;
     }
@@ -3231,7 +3240,7 @@ __device__ void replay_session(const SlowCtx& x, int32_t p, int64_t k, int64_t t
     ne.key = k;
     ne.start = ws;
     ne.end = we;
-    acc_clear(ne);
+    acc_clear(c, ne);
     ne.meta = c.pool_bytes ? (int64_t)(pool_new_block(c, x.st) << 1) : 0;
     actual = new_slot(x, r, p, h, ne);
     if (actual < 0) return;
@@ -3303,7 +3312,7 @@ __device__ void replay_session(const SlowCtx& x, int32_t p, int64_t k, int64_t t
       emit_one(c, x.out, x.st, en);
     }
     if (c.purging) {  // FIRE_AND_PURGE clears the contents; the window stays in flight
-      acc_clear(en);
+      acc_clear(c, en);
       if (c.agg == FW_AGG_HLL) hll_clear(c, pool_block_of(en));
       if (c.agg == FW_AGG_TDIGEST && c.td_olast)
         td_purge(c, ((uint32_t)p << c.log_r) | (uint32_t)actual, pool_block_of(en));
@@ -6304,7 +6313,7 @@ __device__ __forceinline__ FireDecision fire_decide(const DevCfg& c, int64_t wm,
     d.fire = e.cnt > 0;                                 // contents != null (WindowOperator.java:452-459)
     if (c.purging) {                                    // FIRE_AND_PURGE
       if (c.assigner == FW_SESSION)
-        acc_clear(e);                                   // the session stays in the MergingWindowSet
+        acc_clear(c, e);                                   // the session stays in the MergingWindowSet
       else
         d.keep = false;
     }
@@ -6552,7 +6561,7 @@ __device__ __forceinline__ bool pf_upsert(const DevCfg& c, PaneLds& L, const Ent
     if (atomicCAS(&L.tag[s], 0u, 1u) == 0u) {
       L.key[s] = e.key;
       L.cnt[s] = 0;
-      L.sum[s] = 0;
+      L.sum[s] = sum_zero(c.vtype, c.agg);
       L.mn[s] = LMAX;
       L.mx[s] = LMIN;
       L.sel[s] = 0xffffffffu;
@@ -7182,7 +7191,7 @@ __global__ __launch_bounds__(FW_AGG_THREADS) void k_pmerge(DevCfg c, const Parti
     if (!done) d = part[i];
     for (;;) {
       if (!done) {
-        const int tg = lds_slot(L, d.key, d.start);
+        const int tg = lds_slot(L, d.key, d.start, sum_zero(c.vtype, c.agg));
         if (tg >= 0) {
           atomicAdd(&L.cnt[tg], (uint32_t)d.cnt);
           // (HLL: the count only, as LDS_CNT_ONLY in the record path; a partial's sum column is its register count,

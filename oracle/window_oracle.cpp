@@ -408,6 +408,10 @@ class WindowOperatorOracle {
   // Comparator.MinByComparator / MaxByComparator order the field with compareTo: Long / Integer by value,
   // Double by Double.compare (Comparator.java:35-108)
   bool is_float() const { return cfg.value_type == OR_VAL_F64 || cfg.value_type == OR_VAL_F32; }
+  bool reduce_aggregate() const {
+    return cfg.aggregate == OR_AGG_FIRST || cfg.aggregate == OR_AGG_FIRST_MAX || cfg.aggregate == OR_AGG_MINBY ||
+           cfg.aggregate == OR_AGG_MAXBY;
+  }
   // the sum in the field's type: Integer / Short / Byte sums wrap to their width (SumFunction.java:56-107)
   int64_t wrap_sum(int64_t s) const {
     return cfg.value_type == OR_VAL_I32 ? (int64_t)(int32_t)s : cfg.value_type == OR_VAL_I16 ? (int64_t)(int16_t)s
@@ -446,8 +450,15 @@ class WindowOperatorOracle {
         if (java_double_compare(d, a.dmn) < 0) a.dmn = d;
         if (java_double_compare(d, a.dmx) > 0) a.dmx = d;
       }
-      // FloatSum adds in float (SumFunction.java:92-99): every partial sum rounds to float
-      a.dsum = cfg.value_type == OR_VAL_F32 ? (double)((float)a.dsum + (float)d) : a.dsum + d;
+      // FloatSum adds in float (SumFunction.java:92-99): every partial sum rounds to float.
+      // The reduce aggregates (sum(pos) / max(pos) / minBy / maxBy) keep a ReducingState: the element that finds no
+      // state becomes it (HeapReducingState.java:72-84) and SumAggregator.reduce adds the later ones to it
+      // (SumAggregator.java:66-76, SumFunction.java DoubleSum / FloatSum), so the sum starts from the first element
+      // and a window of -0.0 alone sums to -0.0.  CountSumMinMax starts from createAccumulator's +0.0.
+      if (a.cnt == 0 && reduce_aggregate())
+        a.dsum = d;
+      else
+        a.dsum = cfg.value_type == OR_VAL_F32 ? (double)((float)a.dsum + (float)d) : a.dsum + d;
     } else {
       if (a.cnt == 0) {
         a.imn = a.imx = v;

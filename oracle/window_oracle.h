@@ -78,7 +78,10 @@ typedef struct {
  * Row: count = elements, sum = E (f64 bits), min = V, max = low 64 bits of S (an exact register
  * checksum).  AggregateFunction.merge = register-wise max. */
 /* OR_AGG_FIRST: count/sum/min with max = arrival ordinal of the window's first element (the passthrough
- * fields of sum(pos)/min(pos)); ordinals count every element processed, from 0. */
+ * fields of sum(pos)/min(pos)); ordinals count every element processed, from 0.
+ * The reduce aggregates (OR_AGG_FIRST, _FIRST_MAX, _MINBY, _MAXBY) are ReducingStates: a Double / Float sum starts
+ * from the window's first element (HeapReducingState.java:72-84, SumAggregator.java:66-76), so a window of -0.0 alone
+ * sums to -0.0; OR_AGG_COUNT_SUM_MIN_MAX adds to createAccumulator's +0.0. */
 /* OR_AGG_MINBY / OR_AGG_MAXBY: minBy(pos) / maxBy(pos) with first = true (ComparableAggregator.java:72-94):
  * min = the selected field value, max = the arrival ordinal of the selected element. */
 /* OR_AGG_TDIGEST: a merging t-digest (Dunning & Ertl, "Computing extremely accurate quantiles using
