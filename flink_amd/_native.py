@@ -16,6 +16,7 @@ FW_ERR_KEY_GROUP = -4
 FW_ERR_CAPACITY = -5
 FW_ERR_UNSUPPORTED = -6
 FW_ERR_STATE = -7
+FW_ERR_DISPLACED = -8
 
 FW_TUMBLING, FW_SLIDING, FW_SESSION, FW_COUNT = 0, 1, 2, 3
 FW_VAL_I64, FW_VAL_I32, FW_VAL_F64, FW_VAL_I16, FW_VAL_I8, FW_VAL_F32 = 0, 1, 2, 3, 4, 5
@@ -43,7 +44,8 @@ class FwConfig(ctypes.Structure):
                 ("tdigest_compression", ctypes.c_int32), ("tdigest_export", ctypes.c_int32),
                 ("tdigest_quantiles", ctypes.c_double * 3), ("count_evict_after", ctypes.c_int32),
                 ("pad0", ctypes.c_int32), ("row_columns", ctypes.c_int32), ("row_aggregates", ctypes.c_int32),
-                ("row_column_type", ctypes.c_int32 * 8), ("row_aggregate", ctypes.c_int32 * 16)]
+                ("row_column_type", ctypes.c_int32 * 8), ("row_aggregate", ctypes.c_int32 * 16),
+                ("no_panes", ctypes.c_int32), ("pad1", ctypes.c_int32)]
 
 
 class FwRows(ctypes.Structure):

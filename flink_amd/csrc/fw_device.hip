@@ -140,6 +140,12 @@ __device__ __forceinline__ int64_t f64_sortable(int64_t bits) {
 }
 __device__ __forceinline__ int64_t f64_unsortable(int64_t s) { return s >= 0 ? s : (s ^ 0x7fffffffffffffffll); }
 
+// A displaced record: ts - offset + slide < 0 off the slide grid.  Java's truncating % leaves a negative remainder,
+// so getWindowStartWithOffset returns the grid point above ts and SlidingEventTimeWindows.assignWindows gives the
+// record ceil(size / slide) + 1 windows (DESIGN.md "Event-time arithmetic").  Tumbling windows: never asked.
+__device__ __forceinline__ bool displaced(const DevCfg& c, int64_t ts) {
+  return jrem(jadd(jsub(ts, c.offset), c.slide), c.slide, c.mag_slide, c.l_slide) < 0;
+}
 // ------------------------------------------------------------------ record classes
 enum { CLS_NORMAL = 0, CLS_SLOW = 1, CLS_LATE = 2, CLS_SKIP = 3, CLS_BADTS = 4 };
 
@@ -153,7 +159,7 @@ __device__ __forceinline__ int num_windows(const DevCfg& c, int64_t ts, int64_t*
   *last_start = last;
   int k = 0;
   const int64_t lo = jsub(ts, c.size);
-  for (int64_t s = last; s > lo && k <= c.wpr; s = jsub(s, c.slide)) k++;
+  for (int64_t s = last; s > lo && k < c.wpr; s = jsub(s, c.slide)) k++;  // (wpr counts a displaced record's extra window)
   return k;
 }
 
@@ -194,7 +200,10 @@ __device__ __forceinline__ int classify(const DevCfg& c, int64_t wm, int64_t ts,
   if (c.panes) {
     // allowedLateness 0: a window whose maxTimestamp <= wm has fired (or had no contents) and is never
     // evaluated again, so adding the element to its pane adds it to exactly the windows that are not
-    // late (WindowOperator.java:379-407); only when the newest window is late is the element dropped
+    // late (WindowOperator.java:379-407); only when the newest window is late is the element dropped.
+    // A displaced record has one window more than a pane reaches: the host refuses its push before anything is
+    // queued (k_displaced_any, fw_runtime.cpp refuse_displaced) unless the watermark already makes all its windows
+    // late, so the ones that arrive here are dropped below exactly as the reference drops them.
     const int64_t last = wstart(ts, c.offset, c.slide, c.mag_slide, c.l_slide);
     if (last_out) {
       *last_out = last;
@@ -8464,6 +8473,19 @@ void launch_classify_hist(const DevCfg& c, int64_t wm, const int64_t* key, const
 __global__ void k_rsv_reset(uint32_t* rsv, int32_t words, const Status* st) {
   if (__hip_atomic_load(&st->suspended, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
   for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < words; i += gridDim.x * blockDim.x) rsv[i] = 0u;
+}
+// panes: does the batch hold a displaced record that is not Long.MIN_VALUE?  *flag |= 1 (zeroed by the caller)
+__global__ __launch_bounds__(256) void k_displaced_any(DevCfg c, const int64_t* __restrict__ ts, int64_t n, int32_t* flag) {
+  bool any = false;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t t = ts[i];
+    any |= t != LMIN && displaced(c, t);
+  }
+  if (__any(any) && __lane_id() == 0) atomicOr(flag, 1);
+}
+void launch_displaced_any(const DevCfg& c, const int64_t* ts, int64_t n, int32_t* flag, hipStream_t s) {
+  const unsigned blocks = (unsigned)std::min<int64_t>(1024, (n + 255) / 256);
+  hipLaunchKernelGGL(k_displaced_any, dim3(blocks), dim3(256), 0, s, c, ts, n, flag);
 }
 void launch_rsv_reset(uint32_t* rsv, int32_t words, const Status* st, hipStream_t s) {
   hipLaunchKernelGGL(k_rsv_reset, dim3((unsigned)std::min(64, (words + 255) / 256)), dim3(256), 0, s, rsv, words, st);

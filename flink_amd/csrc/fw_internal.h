@@ -114,7 +114,7 @@ struct TdCent;
 struct DevCfg {
   int32_t assigner, vtype, key_kind, purging;
   int32_t side_output, max_par, kg0, n_kg;
-  int32_t log_s, P, log_r, wpr;  // wpr = max windows per record
+  int32_t log_s, P, log_r, wpr;  // wpr = max windows per record: sliding ceil(size / slide) + 1 (a displaced record's extra window; panes refuse those: + 0)
   int64_t size, slide, offset, gap, lateness;
   int32_t diag;                  // FW_DIAG ablation bits (diagnostic builds of the timing only; 0 in production)
   // the field's width (FW_VAL_I16 / I8 / F32 are kept as I32 / F64 inside): sums wrap to sum_bits (64, 32, 16
@@ -494,6 +494,8 @@ void launch_scatter(const DevCfg& c, int64_t wm, const int64_t* key, const int64
 bool rsv_eligible(const DevCfg& c);
 // the single-pass words (P + FW_RSV_WORDS) zeroed after the batch's aggregate, unless the push suspended
 void launch_rsv_reset(uint32_t* rsv, int32_t words, const Status* st, hipStream_t_ s);
+// panes: *flag |= 1 when ts[0 .. n) holds a displaced record (ts - offset + slide < 0 off the slide grid)
+void launch_displaced_any(const DevCfg& c, const int64_t* ts, int64_t n, int32_t* flag, hipStream_t_ s);
 void launch_scatter_rsv(const DevCfg& c, int64_t wm, const int64_t* key, const int64_t* ts, const int64_t* val,
                         const int32_t* kh, int64_t n, int32_t T, PRec* part, uint32_t* rsv, int64_t rcap, hipStream_t_ s);
 // hot: chunk splitting of long partitions (nullptr = one workgroup per partition); n = records of the push

@@ -126,6 +126,7 @@ struct fw_op {
   bool td_export = false;    // FW_AGG_TDIGEST: fired rows keep their centroids (DevRows::dig)
   int64_t dig_stride = 0;    // words per row of DevRows::dig (t-digest export: 1 + delta; FW_AGG_ROW: 1 + aggregates)
   int64_t* iota = nullptr;   // FW_AGG_ROW: 0, 1, ... (a record's value is its index in the push)
+  int32_t* d_disp = nullptr;  // panes: the displaced-record check's flag (refuse_displaced)
 
   DevRows out{};
   DevSide side{};
@@ -722,6 +723,44 @@ int push_count(fw_op* op, const int64_t* key, const int64_t* val, int64_t n) {
 }
 
 hipStream_t input_stream_of(const fw_op* op);  // the stream device pushes read their columns on
+// ---- displaced records (DESIGN.md "Event-time arithmetic"): ts - offset + slide < 0 off the slide grid.  The reference
+// gives such a record size / slide + 1 windows, and the pane that would hold it reaches only size / slide of them,
+// so an operator that keeps panes refuses the whole push before anything of it is queued or copied: the state, the
+// counters and the pending rows are those before the call.  Once the watermark has reached offset + size - slide - 1
+// every window of every displaced record is late (its newest window starts at offset - slide at the latest) and
+// classify drops the record as the reference does, so pushes are checked only until then: a stream of ordinary
+// timestamps pays for the check before its first watermark only.
+bool displaced_possible(const fw_op* op) {
+  if (!op->dc.panes) return false;
+  return (__int128)op->wm < (__int128)op->dc.offset + op->dc.size - op->dc.slide - 1;
+}
+int displaced_error(fw_op* op) {
+  return set_err(op, FW_ERR_DISPLACED,
+                 "Record with timestamp < offset - slide off the slide grid: the reference assigns it size / slide + 1 "
+                 "windows (Java's truncating %% in TimeWindow.getWindowStartWithOffset), which sliding windows kept as "
+                 "panes cannot hold.  Nothing of the push was taken.  Create the operator with no_panes for such "
+                 "timestamps.");
+}
+int refuse_displaced_host(fw_op* op, const int64_t* ts, int64_t n) {
+  if (!displaced_possible(op)) return FW_OK;
+  const int64_t off = op->dc.offset, slide = op->dc.slide;
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t t = (int64_t)((uint64_t)ts[i] - (uint64_t)off + (uint64_t)slide);
+    if (ts[i] != INT64_MIN && t % slide < 0) return displaced_error(op);
+  }
+  return FW_OK;
+}
+// s: the stream the caller ordered the columns' producer before
+int refuse_displaced_device(fw_op* op, const int64_t* ts, int64_t n, hipStream_t s) {
+  if (n <= 0 || !displaced_possible(op)) return FW_OK;
+  int32_t flag = 0;
+  HIP_OR_RETURN(op, hipMemsetAsync(op->d_disp, 0, sizeof(int32_t), s));
+  fwdev::launch_displaced_any(op->dc, ts, n, op->d_disp, s);
+  HIP_OR_RETURN(op, hipGetLastError());
+  HIP_OR_RETURN(op, hipMemcpyAsync(&flag, op->d_disp, sizeof flag, hipMemcpyDeviceToHost, s));
+  HIP_OR_RETURN(op, hipStreamSynchronize(s));
+  return flag ? displaced_error(op) : FW_OK;
+}
 // FW_AGG_ROW input of a push: the caller's columns (column j of the push's record i at cols[j * stride + i]) and NULL
 // masks (nullptr = none)
 struct RowIn {
@@ -932,9 +971,11 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
 // ---- pre-shuffle combining (fw_combine_extract_device / fw_push_partials_device)
 // tumbling windows, or sliding windows kept as panes (size % slide == 0): a pane's partial is classified by its
 // start exactly as each of its elements is (they all share the pane's newest window), so merging it at the receiver
-// equals pushing its records (round 4)
+// equals pushing its records (round 4).  A displaced record would break that (its newest window is the one above its
+// pane's); the combiner is a pane operator whose watermark never moves, so it refuses every push that holds one
+// (refuse_displaced_*), and a pane's start, being on the grid, is never displaced itself.
 bool combine_eligible(const fw_config& c) {
-  const bool panes = c.assigner == FW_SLIDING && c.slide > 0 && c.size > c.slide && c.size % c.slide == 0 &&
+  const bool panes = c.assigner == FW_SLIDING && c.slide > 0 && c.size > c.slide && c.size % c.slide == 0 && !c.no_panes &&
                      !(getenv("FW_NO_PANES") && atoi(getenv("FW_NO_PANES")));
   return (c.assigner == FW_TUMBLING || panes) && c.aggregate == FW_AGG_COUNT_SUM_MIN_MAX &&
          c.allowed_lateness == 0 && !c.side_output && (c.key_kind == FW_KEY_LONG || c.key_kind == FW_KEY_INT);
@@ -1108,9 +1149,14 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
       unsupported = true;
     }
   }
-  if (!msg[0] && cfg.aggregate >= FW_AGG_FIRST && cfg.aggregate <= FW_AGG_FIRST_MAX && cfg.assigner == FW_SLIDING && cfg.slide > 0 &&
-      (cfg.size + cfg.slide - 1) / cfg.slide > 65535) {
-    snprintf(msg, sizeof msg, "the first-element aggregate takes at most 65535 windows per element");
+  // a partitioned record carries its window count in 16 bits: beside the batch index of the ordinal aggregates, and
+  // the HyperLogLog / t-digest / Table fan-out loops read it through the same mask (+ 1: a displaced record's extra
+  // window, DESIGN.md "Event-time arithmetic")
+  if (!msg[0] && cfg.aggregate != FW_AGG_COUNT_SUM_MIN_MAX && cfg.assigner == FW_SLIDING && cfg.slide > 0 &&
+      (cfg.size + cfg.slide - 1) / cfg.slide + 1 > 65535) {
+    snprintf(msg, sizeof msg, cfg.aggregate >= FW_AGG_FIRST && cfg.aggregate <= FW_AGG_FIRST_MAX
+                                  ? "the first-element aggregate takes at most 65535 windows per element"
+                                  : "this aggregate takes at most 65535 windows per element");
     unsupported = true;
   }
   fw_op* op = new fw_op();
@@ -1178,13 +1224,19 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
   c.lateness = cfg.allowed_lateness;
   // FW_DIAG: ablation bits for pricing kernel stages in diagnostic runs only (results are wrong)
   if (const char* d = getenv("FW_DIAG")) c.diag = atoi(d);
-  c.wpr = cfg.assigner == FW_SLIDING ? (int32_t)((cfg.size + cfg.slide - 1) / cfg.slide) : 1;
   // sliding windows whose size is a multiple of the slide, without allowed lateness, are kept as panes:
-  // one state update per element instead of size/slide (DevCfg::panes; FW_NO_PANES=1 disables it)
+  // one state update per element instead of size/slide (DevCfg::panes; FW_NO_PANES=1 or fw_config::no_panes
+  // disables it)
   c.panes = cfg.assigner == FW_SLIDING && cfg.allowed_lateness == 0 && cfg.size > cfg.slide &&
             cfg.size % cfg.slide == 0 && cfg.aggregate != FW_AGG_HLL &&  // (HLL, t-digest, rows: a block per window)
-            cfg.aggregate != FW_AGG_TDIGEST && cfg.aggregate != FW_AGG_ROW &&
+            cfg.aggregate != FW_AGG_TDIGEST && cfg.aggregate != FW_AGG_ROW && !cfg.no_panes &&
             !(getenv("FW_NO_PANES") && atoi(getenv("FW_NO_PANES")));
+  // windows per record, at most: ceil(size / slide), and one more for a displaced record (ts - offset + slide < 0
+  // off the slide grid: Java's truncating % puts its "last start" on the grid point above ts, and
+  // SlidingEventTimeWindows.assignWindows walks down from there; DESIGN.md "Event-time arithmetic").  Every
+  // per-record buffer, bound and index of the windows path is sized by it.  Panes refuse displaced records
+  // (classify), so a pane record has one entry.
+  c.wpr = cfg.assigner == FW_SLIDING ? (int32_t)((cfg.size + cfg.slide - 1) / cfg.slide) + (c.panes ? 0 : 1) : 1;
   if (cfg.assigner != FW_SESSION) {
     make_div_inv((uint64_t)c.size, &c.mag_size, &c.l_size);
     make_div_inv((uint64_t)c.slide, &c.mag_slide, &c.l_slide);
@@ -1278,6 +1330,7 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
     HIP_OR_RETURN(op, dmalloc(&op->iota, (size_t)mb));
     HIP_OR_RETURN(op, hipMemcpy(op->iota, h.data(), (size_t)mb * sizeof(int64_t), hipMemcpyHostToDevice));
   }
+  if (c.panes) HIP_OR_RETURN(op, dmalloc(&op->d_disp, 1));
   c.wide = op->sc[0].wide;  // (every push sets its own set's word)
   // single-pass scatter: a partition's run may take twice its share of the largest batch (part holds mb PRecs
   // = 2 mb compact records), whole 128-byte lines apart
@@ -1509,6 +1562,7 @@ void fw_destroy(fw_op* op) {
   dfree(op->hoff);
   dfree(op->hoff_tmp);
   dfree(op->iota);
+  dfree(op->d_disp);
   for (auto& pr : op->prof_pending) {
     (void)hipEventDestroy(pr.a);
     (void)hipEventDestroy(pr.b);
@@ -1531,6 +1585,7 @@ int fw_push_batch(fw_op* op, const int64_t* key, const int64_t* ts, const void* 
   if (op->cfg.key_kind == FW_KEY_HASHED && n > 0 && !key_hash)
     return set_err(op, FW_ERR_ARG, "key_hash required for FW_KEY_HASHED");
   HIP_OR_RETURN(op, hipSetDevice(op->device));
+  if (int rc = refuse_displaced_host(op, ts, n)) return rc;
   for (int64_t b = 0; b < n; b += op->max_batch) {
     const int64_t m = std::min(op->max_batch, n - b);
     HIP_OR_RETURN(op, hipMemcpyAsync(op->in_key, key + b, m * 8, hipMemcpyHostToDevice, op->stream));
@@ -1558,6 +1613,7 @@ int push_device_batches(fw_op* op, const int64_t* key, const int64_t* ts, const 
   if (op->cfg.key_kind == FW_KEY_HASHED && n > 0 && !key_hash)
     return set_err(op, FW_ERR_ARG, "key_hash required for FW_KEY_HASHED");
   HIP_OR_RETURN(op, hipSetDevice(op->device));
+  if (int rc = refuse_displaced_device(op, ts, n, async_ok ? input_stream_of(op) : op->stream)) return rc;
   for (int64_t b = 0; b < n; b += op->max_batch) {
     const int64_t m = std::min(op->max_batch, n - b);
     int rc = push_device(op, key + b, ts + b, (const int64_t*)val + b, key_hash ? key_hash + b : nullptr, m, async_ok);

@@ -42,7 +42,7 @@ class GpuWindowOperator:
     def __init__(self, assigner: WindowAssigner, aggregate=CountSumMinMax(), trigger: Trigger = None,
                  allowed_lateness=0, side_output=False, key_type="long", max_parallelism=128,
                  key_group_range: KeyGroupRange = None, device=0, expected_entries=0, max_batch=0,
-                 sub_partitions=0, async_input=True):
+                 sub_partitions=0, async_input=True, no_panes=False):
         trigger = trigger or EventTimeTrigger.create()
         if not isinstance(getattr(trigger, "nested", trigger), EventTimeTrigger):
             raise ValueError("GpuWindowOperator takes EventTimeTrigger or PurgingTrigger.of(EventTimeTrigger); "
@@ -78,6 +78,10 @@ class GpuWindowOperator:
         c.sub_partitions = sub_partitions
         c.allowed_lateness = allowed_lateness
         c.expected_entries = expected_entries
+        # sliding windows are kept as panes where size % slide == 0 (one state update per record); panes refuse a
+        # displaced record (a pre-epoch timestamp that the reference gives size / slide + 1 windows,
+        # FW_ERR_DISPLACED).  no_panes keeps windows, which take every timestamp exactly.
+        c.no_panes = int(bool(no_panes))
         c.max_batch = max_batch
         self.assigner, self.aggregate, self.trigger = assigner, aggregate, trigger
         self.allowed_lateness = allowed_lateness

@@ -35,6 +35,10 @@ extern "C" {
 #define FW_ERR_CAPACITY (-5)     /* state could not be stored (HBM exhausted) */
 #define FW_ERR_UNSUPPORTED (-6)  /* configuration not offered on the GPU path */
 #define FW_ERR_STATE (-7)        /* corrupted / inconsistent handle state */
+#define FW_ERR_DISPLACED (-8)    /* sliding windows kept as panes: the push holds a record with ts - offset + slide < 0
+                                    off the slide grid, to which the reference assigns size / slide + 1 windows
+                                    (Java's truncating % in TimeWindow.getWindowStartWithOffset).  The whole push is
+                                    refused and nothing changed; fw_config::no_panes keeps windows, which take it */
 
 /* ---- assigner, value and key kinds ---- */
 #define FW_TUMBLING 0 /* api/windowing/assigners/TumblingEventTimeWindows.java:53-73 */
@@ -173,6 +177,12 @@ typedef struct fw_config {
   int32_t row_aggregates;      /* FW_AGG_ROW: aggregates of a row, 1 .. 16                       */
   int32_t row_column_type[8];  /* FW_AGG_ROW: FW_VAL_* of each column                            */
   int32_t row_aggregate[16];   /* FW_AGG_ROW: FW_ROW_* << 8 | column                             */
+  int32_t no_panes;            /* FW_SLIDING: 1 = keep windows, not panes, also where size % slide == 0 and the
+                                  lateness is 0.  Panes refuse a displaced record (a pre-epoch timestamp with
+                                  ts - offset + slide < 0 off the slide grid, which the reference assigns
+                                  size / slide + 1 windows; FW_ERR_DISPLACED); windows take it exactly.  Appended:
+                                  no earlier offset moved */
+  int32_t pad1;
 } fw_config;
 
 typedef struct fw_op fw_op;

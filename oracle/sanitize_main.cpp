@@ -20,24 +20,68 @@ static uint64_t sm(uint64_t z) {
   return z ^ (z >> 31);
 }
 
+// the quotient the device computes from (m, l): t1 = mulhi(m, n); (t1 + ((n - t1) >> 1)) >> (l - 1); l == 0: d == 1
+static uint64_t div_inv_host(uint64_t n, uint64_t m, int32_t l) {
+  if (l == 0) return n;
+  const uint64_t t1 = (uint64_t)(((unsigned __int128)m * n) >> 64);
+  return (t1 + ((n - t1) >> 1)) >> (l - 1);
+}
+
 static int check_div_inv() {
-  // the quotient the device computes from (m, l): t1 = mulhi(m, n); (t1 + ((n - t1) >> 1)) >> (l - 1)
   int bad = 0;
-  const uint64_t ds[] = {1, 2, 3, 7, 1000, 60000, 1000003, 86400000ull, (1ull << 40) + 5, ~0ull >> 1};
+  std::vector<uint64_t> ds = {1, 2, 3, 7, 1000, 60000, 1000003, 86400000ull, (1ull << 40) + 5, ~0ull >> 1,
+                              (1ull << 32) + 1, (1ull << 40) + 15, (1ull << 61) + 1, (1ull << 62) + 1};
+  for (int k = 2; k <= 62; k++) {  // 2^k - 1 and 2^k + 1
+    ds.push_back((1ull << k) - 1);
+    ds.push_back((1ull << k) + 1);
+  }
+  const uint64_t top = 1ull << 63;
   for (uint64_t d : ds) {
     uint64_t m;
     int32_t l;
     make_div_inv(d, &m, &l);
-    for (int i = 0; i < 20000; i++) {
-      const uint64_t n = i < 10 ? (uint64_t)i : (i < 20 ? ~0ull - (uint64_t)(i - 10) : sm((uint64_t)i * 7919u + d));
-      uint64_t q;
-      if (l == 0) {
-        q = n;
-      } else {
-        const uint64_t t1 = (uint64_t)(((unsigned __int128)m * n) >> 64);
-        q = (t1 + ((n - t1) >> 1)) >> (l - 1);
+    if ((d == 1) != (l == 0)) bad++;
+    if (d == (1ull << 61) + 1 && l != 62) bad++;
+    if (d == (1ull << 62) + 1 && l != 63) bad++;
+    std::vector<uint64_t> ns = {top, top - 1, top + 1};
+    // the multiples of d next to 2^63 (|Long.MIN_VALUE|, the largest dividend jrem forms) and to 2^64, and their neighbours
+    for (uint64_t q : {(uint64_t)(top / d), (uint64_t)(top / d + 1), (uint64_t)(~0ull / d)})
+      for (int e = -1; e <= 1; e++)
+        if (q >= 1 && q <= ~0ull / d) ns.push_back(q * d + (uint64_t)(int64_t)e);
+    for (int i = 0; i < 20000; i++)
+      ns.push_back(i < 10 ? (uint64_t)i : (i < 20 ? ~0ull - (uint64_t)(i - 10) : sm((uint64_t)i * 7919u + d)));
+    for (uint64_t n : ns)
+      if (div_inv_host(n, m, l) != n / d) bad++;
+  }
+  return bad;
+}
+
+// the composition the device code makes of it (flink_amd/csrc/fw_device.hip jrem / wstart): |t| with the dividend's
+// sign, also for Long.MIN_VALUE, against 128-bit truncating arithmetic wrapped to 64 bits
+static int check_window_start() {
+  int bad = 0;
+  const int64_t sizes[] = {1, 3, 7, 1000, 1023, 1025, 1000003, (1ll << 32) + 1, (1ll << 40) + 15, (1ll << 61) + 1,
+                           (1ll << 62) + 1};
+  for (int64_t d : sizes) {
+    uint64_t m;
+    int32_t l;
+    make_div_inv((uint64_t)d, &m, &l);
+    const int64_t offs[] = {0, d - 1, -(d - 1), -28800000};
+    for (int64_t off : offs) {
+      for (int i = 0; i < 4000; i++) {
+        int64_t ts;
+        if (i < 21) ts = (int64_t)((uint64_t)off + (uint64_t)((i / 3 - 3) * (__int128)d) + (uint64_t)(int64_t)(i % 3 - 1));
+        else if (i < 24) ts = INT64_MIN + (i - 21);
+        else if (i < 27) ts = INT64_MAX - (i - 24);
+        else ts = (int64_t)sm((uint64_t)i * 104729u + (uint64_t)d) >> (i % 40);
+        const int64_t t = (int64_t)((uint64_t)ts - (uint64_t)off + (uint64_t)d);
+        const uint64_t u = t < 0 ? (uint64_t)0 - (uint64_t)t : (uint64_t)t;
+        const uint64_t r = u - div_inv_host(u, m, l) * (uint64_t)d;
+        const int64_t rem = t < 0 ? -(int64_t)r : (int64_t)r;
+        const int64_t got = (int64_t)((uint64_t)ts - (uint64_t)rem);
+        const __int128 want_rem = (__int128)t % (__int128)d;  // (C++ truncates as Java does)
+        if (rem != (int64_t)want_rem || got != oracle_window_start(ts, off, d)) bad++;
       }
-      if (q != n / d) bad++;
     }
   }
   return bad;
@@ -83,6 +127,11 @@ int main() {
   const int bad = check_div_inv();
   if (bad) {
     fprintf(stderr, "make_div_inv: %d wrong quotients\n", bad);
+    return 1;
+  }
+  const int bad_ws = check_window_start();
+  if (bad_ws) {
+    fprintf(stderr, "window start through the reciprocal: %d wrong\n", bad_ws);
     return 1;
   }
   oracle_cfg base{};
