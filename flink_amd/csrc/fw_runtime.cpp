@@ -35,7 +35,9 @@ namespace {
 
 // per-batch scratch; two sets alternate so a push can be resumed while the next one is classified
 struct Scratch {
-  uint32_t* hist = nullptr;      // (P+2) x T histogram, scanned in place into offsets
+  // (P+2) x T histogram, scanned in place into offsets: partition p's run in part starts at hist[p * T]; rows P and
+  // P + 1 are the ordered-path records per tile, scanned and raw
+  uint32_t* hist = nullptr;
   uint32_t* scan_tmp = nullptr;
   PRec* part = nullptr;          // the batch's normal records, partition-major
   int64_t *sk = nullptr, *stt = nullptr, *sv = nullptr;  // ordered-path list
@@ -61,20 +63,11 @@ struct Scratch {
   int64_t hn = 0;
   const uint32_t* hregs = nullptr;
   const uint32_t* hoff = nullptr;
-  // gathered batches (fwdev::gather_mode): runs table [T8][P] and its transpose, the partitions' virtual
-  // offsets (P + 1) and the ordered-path rows (2 x T8); T is then the batch's FW_GTILE tiles
-  uint32_t *rt = nullptr, *rt_t = nullptr, *voffs = nullptr, *gsrow = nullptr, *gcb = nullptr;
-  bool gather = false;
   // dense batches: the single-pass scatter's run lengths and flags (fwdev::launch_scatter_rsv), P + FW_RSV_WORDS
   uint32_t* rsv = nullptr;
   bool single = false;  // the set's latest batch went through it (its runs are then at p * fw_op::rcap ...)
   // DevCfg::wide of the set's latest batch: a word of rsv (zeroed with it) when the batch took the single pass
   int32_t* wide_word(int32_t P) const { return single ? reinterpret_cast<int32_t*>(rsv + P + FW_RSV_WIDE) : wide; }
-  // the ordered-path rows of the batch: scanned counts per tile, then raw counts
-  const uint32_t* srow(int32_t P) const { return gather ? gsrow : hist + (int64_t)P * T; }
-  // the partitions' runs in part: offsets offs()[p * offT()] (a gathered batch: regrouped, virtual offsets)
-  const uint32_t* offs() const { return gather ? voffs : hist; }
-  int32_t offT() const { return gather ? 1 : T; }
 };
 
 }  // namespace
@@ -243,16 +236,6 @@ int alloc_scratch(fw_op* op, Scratch& s, int64_t mb, int64_t m) {
     HIP_OR_RETURN(op, dmalloc(&s.rowc, (size_t)(mb * op->dc.row_nc)));
     HIP_OR_RETURN(op, dmalloc(&s.rown, (size_t)mb));
   }
-  DevCfg probe = op->dc;
-  probe.compact = 1;
-  if (fwdev::gather_mode(probe, 1)) {
-    const int64_t t8 = std::min<int64_t>((mb + FW_GTILE - 1) / FW_GTILE, FW_GMAX_T);
-    HIP_OR_RETURN(op, dmalloc(&s.rt, (size_t)(t8 * op->dc.P)));
-    HIP_OR_RETURN(op, dmalloc(&s.rt_t, (size_t)(t8 * op->dc.P)));
-    HIP_OR_RETURN(op, dmalloc(&s.voffs, (size_t)op->dc.P + 1));
-    HIP_OR_RETURN(op, dmalloc(&s.gsrow, (size_t)(2 * t8)));
-    HIP_OR_RETURN(op, dmalloc(&s.gcb, (size_t)op->dc.P + 1));
-  }
   return FW_OK;
 }
 void free_scratch(Scratch& s) {
@@ -270,11 +253,6 @@ void free_scratch(Scratch& s) {
   dfree(s.pparts);
   dfree(s.so);
   dfree(s.byv);
-  dfree(s.rt);
-  dfree(s.rt_t);
-  dfree(s.voffs);
-  dfree(s.gsrow);
-  dfree(s.gcb);
 }
 
 // buffers of the split-partition aggregate (AggHot): deltas at record indices, so one Entry per record
@@ -604,25 +582,25 @@ int settle(fw_op* op) {
     }
     if (susp & FW_SUSP_AGG)
       timed(op, K_AGGREGATE, [&] {
-        fwdev::launch_aggregate(c, S.wm, S.part, S.offs(), S.offT(), op->tb, op->prog, 1, S.split ? &op->hot : nullptr,
-                                S.n, op->d_status, op->stream, nullptr, 0, S.single ? S.rsv : nullptr, op->rcap);
+        fwdev::launch_aggregate(c, S.wm, S.part, S.hist, S.T, op->tb, op->prog, 1, S.split ? &op->hot : nullptr,
+                                S.n, op->d_status, op->stream, S.single ? S.rsv : nullptr, op->rcap);
         // the update skipped itself behind the suspension; register max is idempotent, so it reruns whole (and the
         // Table aggregates' adds, which are not, never started)
         if (c.agg == FW_AGG_HLL)
-          fwdev::launch_hll_update(c, S.part, S.offs(), S.offT(), S.n, op->tb, op->d_status, op->stream);
+          fwdev::launch_hll_update(c, S.part, S.hist, S.T, S.n, op->tb, op->d_status, op->stream);
         if (c.agg == FW_AGG_ROW)
-          fwdev::launch_row_update(c, S.part, S.offs(), S.offT(), S.n, op->tb, op->d_status, op->stream);
+          fwdev::launch_row_update(c, S.part, S.hist, S.T, S.n, op->tb, op->d_status, op->stream);
       });
     // after an aggregate suspension the ordered path never started; otherwise it resumes
     if (!c.dense) timed(op, K_SLOW, [&] {
-      fwdev::launch_slow(c, S.wm, S.srow(op->dc.P), S.T, S.sk, S.stt, S.sv, S.skh, op->tb, op->out, op->side, op->d_status,
-                         (susp & FW_SUSP_AGG) ? 0 : 1, op->stream);
+      fwdev::launch_slow(c, S.wm, S.hist + (int64_t)op->dc.P * S.T, S.T, S.sk, S.stt, S.sv, S.skh, op->tb, op->out,
+                         op->side, op->d_status, (susp & FW_SUSP_AGG) ? 0 : 1, op->stream);
     });
     // the t-digest compression skipped itself behind the suspension (it runs once, after the aggregate and the
     // ordered path completed)
     if ((susp & (FW_SUSP_AGG | FW_SUSP_SLOW)) && c.agg == FW_AGG_TDIGEST)
       timed(op, K_TDIGEST, [&] {
-        fwdev::launch_tdigest(c, S.part, S.offs(), S.offT(), S.n, op->tb, op->td, op->d_status, op->stream);
+        fwdev::launch_tdigest(c, S.part, S.hist, S.T, S.n, op->tb, op->td, op->d_status, op->stream);
       });
     // a watermark queued behind the push skipped itself; firing at the latest one is the same as
     // firing at each (nothing was pushed in between)
@@ -805,18 +783,16 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
     else
       c.cbase = (int64_t)base;
   }
-  const bool gather = S.rt && fwdev::gather_mode(c, n);
-  const bool single = !gather && S.rsv && !op->rsv_off && op->rcap > 0 && fwdev::rsv_eligible(c);
+  const bool single = S.rsv && !op->rsv_off && op->rcap > 0 && fwdev::rsv_eligible(c);
   // narrow records: integer fields only (a narrow value is an int32), compact windows from the watermark's on
   static const bool no_narrow = getenv("FW_NO_NARROW") && atoi(getenv("FW_NO_NARROW"));
   c.narrow = single && !op->narrow_off && c.vtype != FW_VAL_F64 && c.log_s >= 1 && !no_narrow;
   c.ndn0 = c.narrow ? 1 << (c.log_s - 1) : 0;
-  const int32_t T = gather ? (int32_t)((n + FW_GTILE - 1) / FW_GTILE) : (int32_t)((n + FW_TILE - 1) / FW_TILE);
+  const int32_t T = (int32_t)((n + FW_TILE - 1) / FW_TILE);
   const int64_t m = (int64_t)(c.P + 1) * T;
   // async input: the batch-only kernels run on bstream, after the aggregate that last used this scratch set
-  // (the same predicate as fw_input_stream, which the caller ordered its producer before: a batch that is not
-  // gathered while gather scratch exists stays on the operator's stream)
-  const bool two = async_ok && input_stream_of(op) == op->bstream && !gather;
+  // (the same predicate as fw_input_stream, which the caller ordered its producer before)
+  const bool two = async_ok && input_stream_of(op) == op->bstream;
   hipStream_t bs = two ? op->bstream : op->stream;
   if (two) HIP_OR_RETURN(op, hipStreamWaitEvent(bs, op->ev_done[nxt], 0));
   if (c.assigner == FW_SESSION) {
@@ -830,53 +806,44 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
   }
   if (single) c.wide = reinterpret_cast<int32_t*>(S.rsv + c.P + FW_RSV_WIDE);  // (zero with the rest of rsv)
   else if (c.compact) HIP_OR_RETURN(op, hipMemsetAsync(S.wide, 0, sizeof(int32_t), bs));
-  if (gather) {
-    // classify, tile-local partition sort, runs table, ordered-path compaction: one pass over the input
-    timed(op, K_SCATTER, [&] {
-      fwdev::launch_stage(c, op->wm, key, ts, val, kh, n, S.part, op->max_batch, S.rt, S.rt_t, S.voffs, S.gsrow, S.gcb, S.sk,
-                          S.stt, S.sv, S.skh, op->side, op->d_status, op->stream);
-    });
+  // dense compact batches: one pass reserves each partition's run piece by piece; the classify / scan /
+  // offset-scatter sequence behind it runs only when that pass could not take the batch (a record without a
+  // compact form, a run beyond rcap)
+  if (single) {  // (rsv is zero: reset behind the set's previous aggregate, k_rsv_reset, or by settle)
+    timed(op, K_SCATTER, [&] { fwdev::launch_scatter_rsv(c, op->wm, key, ts, val, kh, n, T, S.part, S.rsv, op->rcap, bs); },
+          bs, true);
+  }
+  const uint32_t* gate = single ? S.rsv + c.P : nullptr;
+  if (single) {  // (fw_profile: the gated sequence counts as classify)
+    timed(
+        op, K_CLASSIFY,
+        [&] {
+          fwdev::launch_classify_hist(c, op->wm, key, ts, kh, n, T, S.hist, op->d_status, bs, S.rsv);
+          fwdev::launch_scan(S.hist, m, S.scan_tmp, bs, gate);
+          fwdev::launch_scatter(c, op->wm, key, ts, val, kh, n, T, S.hist, S.part, S.sk, S.stt, S.sv, S.skh, op->side,
+                                op->d_status, bs, gate);
+        },
+        bs);
   } else {
-    // dense compact batches: one pass reserves each partition's run piece by piece; the classify / scan /
-    // offset-scatter sequence behind it runs only when that pass could not take the batch (a record without a
-    // compact form, a run beyond rcap)
-    if (single) {  // (rsv is zero: reset behind the set's previous aggregate, k_rsv_reset, or by settle)
-      timed(op, K_SCATTER, [&] { fwdev::launch_scatter_rsv(c, op->wm, key, ts, val, kh, n, T, S.part, S.rsv, op->rcap, bs); },
-            bs, true);
-    }
-    const uint32_t* gate = single ? S.rsv + c.P : nullptr;
-    if (single) {  // (fw_profile: the gated sequence counts as classify)
-      timed(
-          op, K_CLASSIFY,
-          [&] {
-            fwdev::launch_classify_hist(c, op->wm, key, ts, kh, n, T, S.hist, op->d_status, bs, S.rsv);
-            fwdev::launch_scan(S.hist, m, S.scan_tmp, bs, gate);
-            fwdev::launch_scatter(c, op->wm, key, ts, val, kh, n, T, S.hist, S.part, S.sk, S.stt, S.sv, S.skh, op->side,
-                                  op->d_status, bs, gate);
-          },
-          bs);
-    } else {
-      timed(
-          op, K_CLASSIFY,
-          [&] {
-            if (c.assigner == FW_SESSION) fwdev::launch_taint(c, op->wm, key, ts, n, op->d_status, bs);
-            fwdev::launch_classify_hist(c, op->wm, key, ts, kh, n, T, S.hist, op->d_status, bs);
-          },
-          bs);
-      timed(op, K_SCAN, [&] { fwdev::launch_scan(S.hist, m, S.scan_tmp, bs); }, bs);
-      timed(
-          op, K_SCATTER,
-          [&] {
-            fwdev::launch_scatter(c, op->wm, key, ts, val, kh, n, T, S.hist, S.part, S.sk, S.stt, S.sv, S.skh, op->side,
-                                  op->d_status, bs);
-          },
-          bs);
-    }
+    timed(
+        op, K_CLASSIFY,
+        [&] {
+          if (c.assigner == FW_SESSION) fwdev::launch_taint(c, op->wm, key, ts, n, op->d_status, bs);
+          fwdev::launch_classify_hist(c, op->wm, key, ts, kh, n, T, S.hist, op->d_status, bs);
+        },
+        bs);
+    timed(op, K_SCAN, [&] { fwdev::launch_scan(S.hist, m, S.scan_tmp, bs); }, bs);
+    timed(
+        op, K_SCATTER,
+        [&] {
+          fwdev::launch_scatter(c, op->wm, key, ts, val, kh, n, T, S.hist, S.part, S.sk, S.stt, S.sv, S.skh, op->side,
+                                op->d_status, bs);
+        },
+        bs);
   }
   S.single = single;
   op->single_batches += single;
   op->narrow_batches += c.narrow;
-  S.gather = gather;
   S.T = T;
   // minBy / maxBy: the aggregate reads the selected elements' fields back by batch index, possibly after the
   // caller's columns are gone (a resumed push), so the batch keeps its own copy
@@ -930,24 +897,24 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
   timed(
       op, K_AGGREGATE,
       [&] {
-        fwdev::launch_aggregate(cc, op->wm, S.part, S.offs(), S.offT(), op->tb, op->prog, 0, split ? &op->hot : nullptr,
-                                n, op->d_status, op->stream, nullptr, 0, single ? S.rsv : nullptr, op->rcap);
+        fwdev::launch_aggregate(cc, op->wm, S.part, S.hist, S.T, op->tb, op->prog, 0, split ? &op->hot : nullptr,
+                                n, op->d_status, op->stream, single ? S.rsv : nullptr, op->rcap);
         if (cc.agg == FW_AGG_HLL)
-          fwdev::launch_hll_update(cc, S.part, S.offs(), S.offT(), n, op->tb, op->d_status, op->stream);
+          fwdev::launch_hll_update(cc, S.part, S.hist, S.T, n, op->tb, op->d_status, op->stream);
         if (cc.agg == FW_AGG_ROW)
-          fwdev::launch_row_update(cc, S.part, S.offs(), S.offT(), n, op->tb, op->d_status, op->stream);
+          fwdev::launch_row_update(cc, S.part, S.hist, S.T, n, op->tb, op->d_status, op->stream);
       },
       nullptr, cc.dense);  // (the dense aggregate is one kernel)
   if (single) fwdev::launch_rsv_reset(S.rsv, cc.P + FW_RSV_WORDS, op->d_status, op->stream);
   if (!cc.dense)  // (tumbling windows without allowed lateness: no record needs arrival order)
     timed(op, K_SLOW, [&] {
-      fwdev::launch_slow(cc, op->wm, S.srow(cc.P), S.T, S.sk, S.stt, S.sv, S.skh, op->tb, op->out, op->side, op->d_status,
-                         0, op->stream);
+      fwdev::launch_slow(cc, op->wm, S.hist + (int64_t)cc.P * S.T, S.T, S.sk, S.stt, S.sv, S.skh, op->tb, op->out,
+                         op->side, op->d_status, 0, op->stream);
     });
   // the t-digest compression closes the push: after the ordered path too (sessions: its merges and added values)
   if (cc.agg == FW_AGG_TDIGEST)
     timed(op, K_TDIGEST, [&] {
-      fwdev::launch_tdigest(cc, S.part, S.offs(), S.offT(), n, op->tb, op->td, op->d_status, op->stream);
+      fwdev::launch_tdigest(cc, S.part, S.hist, S.T, n, op->tb, op->td, op->d_status, op->stream);
     });
   HIP_OR_RETURN(op, hipGetLastError());
   HIP_OR_RETURN(op, hipEventRecord(op->ev_done[nxt], op->stream));  // the set's last use by this batch (see settle)
@@ -1036,7 +1003,6 @@ int push_partials(fw_op* op, const PartialCols& in, int64_t n, const uint32_t* h
   S.partials = true;
   S.single = false;
   S.split = false;
-  S.gather = false;
   S.wm = op->wm;
   S.compact = 0;
   S.cbase = 0;
@@ -1601,9 +1567,9 @@ int fw_push_batch(fw_op* op, const int64_t* key, const int64_t* ts, const void* 
 
 namespace {
 // the stream a device push reads its columns on: the input stream when async input applies to the operator's
-// batches (push_device's `two`: not with side output, count windows or gathered batches)
+// batches (push_device's `two`: not with side output or count windows)
 hipStream_t input_stream_of(const fw_op* op) {
-  const bool two = op->async_in && !op->dc.side_output && op->cfg.assigner != FW_COUNT && !op->sc[0].rt;
+  const bool two = op->async_in && !op->dc.side_output && op->cfg.assigner != FW_COUNT;
   return two ? op->bstream : op->stream;
 }
 

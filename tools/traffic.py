@@ -32,7 +32,7 @@ def short(name):
 BUCKETS = {
     "k_classify_hist": ("k_classify_hist", "k_taint"),
     "k_scan": ("k_scan_blocks", "k_scan_top", "k_scan_add"),
-    "k_scatter": ("k_scatter_rsv", "k_scatter_staged", "k_scatter", "k_scatter_ordered", "k_stage"),
+    "k_scatter": ("k_scatter_rsv", "k_scatter_staged", "k_scatter", "k_scatter_ordered"),
     "k_aggregate": ("k_aggregate", "k_dt_aggregate", "k_hll_update", "k_chunk_plan", "k_pmerge"),
     "k_slow": ("k_slow",),
     "k_fire": ("k_fire", "k_fire_panes", "k_dt_fire"),
