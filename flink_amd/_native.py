@@ -202,6 +202,10 @@ SIGNATURES = {
                                                   ctypes.c_int64, I64P, I64P]),
     "fw_list_restore_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwListState), ctypes.c_int64,
                                                  ctypes.c_int64]),
+    "fw_count_snapshot_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwListState), ctypes.c_int64,
+                                                   ctypes.c_int64, I64P, I64P]),
+    "fw_count_restore_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwListState), ctypes.c_int64,
+                                                  ctypes.c_int64]),
     "fw_generate_device": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, VP,
                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, VP, VP, VP, VP, VP]),
 }

@@ -5823,8 +5823,13 @@ __global__ __launch_bounds__(64) void k_td_large_compact(DevCfg c, TdBuf td, Sta
 // On the GPU: every record gets its key's slot, the batch is sorted stably by slot, so a key's records form one run in arrival order, the record at rank r of its run is the
 // key's element number seq = count + r + 1; it fires when seq % slide == 0 over the elements seq - w + 1 .. seq
 // (w = min(wl, seq)), read from the run and from the key's ring of its last wl - 1 earlier elements.
-__device__ __forceinline__ int32_t cnt_slot(const DevCount& cw, int64_t key, Status* st) {
-  uint32_t s = (uint32_t)fmix64((uint64_t)key ^ 0x3C6EF372FE94F82Bull) & cw.cap_mask;
+__device__ __forceinline__ uint32_t cnt_home(const DevCount& cw, int64_t key) {
+  return (uint32_t)fmix64((uint64_t)key ^ 0x3C6EF372FE94F82Bull) & cw.cap_mask;
+}
+// kg_of(): the key's key group, asked for by the lane that claims the key's slot only (DevCount::mkg)
+template <class KG>
+__device__ __forceinline__ int32_t cnt_slot(const DevCount& cw, int64_t key, Status* st, KG kg_of) {
+  uint32_t s = cnt_home(cw, key);
   for (uint32_t probes = 0; probes <= cw.cap_mask;) {
     // relaxed agent-scope (L2) loads: an acquire here would invalidate the CU's L1 on every record; the publisher
     // below stores the key and slot write-through and waits for them before it stores the state
@@ -5845,6 +5850,7 @@ __device__ __forceinline__ int32_t cnt_slot(const DevCount& cw, int64_t key, Sta
       const int32_t slot = atomicAdd(cw.nslots, 1);
       __hip_atomic_store(&cw.mkey[s], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&cw.mslot[s], (uint32_t)slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (slot < cw.max_keys) cw.mkg[slot] = kg_of();  // (read by a later kernel only: the snapshot)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __hip_atomic_store(&cw.mstate[s], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (slot >= cw.max_keys) {
@@ -5857,10 +5863,12 @@ __device__ __forceinline__ int32_t cnt_slot(const DevCount& cw, int64_t key, Sta
   atomicOr(&st->flags, FW_STATUS_STATE_LOST);
   return -1;
 }
-__global__ __launch_bounds__(256) void k_cnt_slots(DevCount cw, const int64_t* __restrict__ key, int64_t n,
-                                                   uint32_t none, Status* st) {
+__global__ __launch_bounds__(256) void k_cnt_slots(DevCount cw, const int64_t* __restrict__ key,
+                                                   const int32_t* __restrict__ kh, int32_t key_kind, int32_t max_par,
+                                                   int64_t n, uint32_t none, Status* st) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t slot = cnt_slot(cw, key[i], st);
+    const int64_t k = key[i];
+    const int32_t slot = cnt_slot(cw, k, st, [&] { return key_group(key_hash_of(key_kind, k, kh, i), max_par); });
     cw.sk[0][i] = slot < 0 ? none : (uint32_t)slot;
     cw.sv[0][i] = (uint32_t)i;
   }
@@ -5996,6 +6004,102 @@ __global__ __launch_bounds__(256) void k_cnt_count(DevCount cw, const uint32_t* 
     const uint32_t g = sk[i];
     if (g == none || (i + 1 < n && sk[i + 1] == g)) continue;  // the last record of the key's run
     cw.cnt[g] += cw.send[g] - cw.sbeg[g];
+  }
+}
+
+// ---- count windows: keyed state per key group, in the list operator's logical form (fw_count_snapshot_key_group).
+// A key's row is what EvictingWindowOperator holds for it after its k = cnt elements, reduced to what a later firing
+// can still read.  After the firing at f = k - k % slide the reference's list keeps min(size, f) elements
+// (CountEvictor.java:63-78, before or after the function; EvictingWindowOperator.java:334-366 writes the rest back),
+// then grows by the k - f elements since; a later firing reads at most the last wl - 1 elements before its own.
+__device__ __forceinline__ int64_t cnt_state_len(const DevCount& cw, int64_t k) {
+  const int64_t f = k - k % cw.slide;
+  const int64_t lref = f == 0 ? k : min(cw.size, f) + (k - f);
+  return min(lref, cw.wl - 1);
+}
+// pass 1 over the key map and one word beyond it (the scans' totals)
+__global__ __launch_bounds__(256) void k_cnt_snap_count(DevCount cw, int32_t kg, uint32_t* __restrict__ nl,
+                                                        uint32_t* __restrict__ ne) {
+  const int64_t cap = (int64_t)cw.cap_mask + 1;
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= cap; s += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t l = 0, e = 0;
+    if (s < cap && cw.mstate[s] == 2u) {
+      const uint32_t slot = cw.mslot[s];
+      if (slot < (uint32_t)cw.max_keys && cw.mkg[slot] == kg) {
+        const int64_t k = cw.cnt[slot], m = cnt_state_len(cw, k);
+        if (m > 0 || k % cw.slide != 0) {  // (a key with neither elements nor a trigger count has no state)
+          l = 1;
+          e = (uint32_t)m;
+        }
+      }
+    }
+    nl[s] = l;
+    ne[s] = e;
+  }
+}
+// pass 2: nl / ne scanned; position s holds a list iff nl steps there.  The list's elements are the key's last
+// ne[s + 1] - ne[s], oldest first, at the scanned offset: no two lists interleave
+__global__ __launch_bounds__(256) void k_cnt_snap_rows(DevCount cw, const uint32_t* __restrict__ nl,
+                                                       const uint32_t* __restrict__ ne, CountStateCols d) {
+  const int64_t cap = (int64_t)cw.cap_mask + 1, ring = cw.wl - 1;
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t i = nl[s];
+    if (nl[s + 1] == i) continue;
+    const uint32_t slot = cw.mslot[s];
+    const int64_t k = cw.cnt[slot], m = (int64_t)(ne[s + 1] - ne[s]);
+    d.key[i] = cw.mkey[s];
+    d.start[i] = LMIN;  // GlobalWindow: no timers (GlobalWindows' trigger state is CountTrigger's count alone)
+    d.end[i] = LMAX;
+    d.trigger_count[i] = k % cw.slide;  // CountTrigger clears its count at each firing (CountTrigger.java:47-55)
+    d.timer[i] = 0;
+    d.n_elems[i] = m;
+    int64_t at = ne[s];
+    for (int64_t q = k - m + 1; q <= k; q++, at++) {  // (m > 0 only with ring > 0)
+      const int64_t r = (int64_t)slot * ring + (q - 1) % ring;
+      d.ts[at] = LMIN;  // count handles keep no timestamps; CountEvictor and GlobalWindow rows read none
+      d.val[at] = cw.ring_v[r];
+      d.ordinal[at] = cw.ring_o[r];
+    }
+  }
+}
+// restore, first pass (the host has checked the lists' own columns): nothing is written to the handle's state;
+// res[0] counts the lists whose key is in the map already, res[1] those that need a slot
+__global__ __launch_bounds__(256) void k_cnt_restore_check(DevCount cw, CountStateCols src, int64_t n, int32_t* res) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if (src.n_elems[i] == 0 && src.trigger_count[i] == 0) continue;  // no state: takes no slot
+    const int64_t key = src.key[i];
+    uint32_t s = cnt_home(cw, key);
+    bool found = false;
+    for (uint32_t probes = 0; probes <= cw.cap_mask; probes++, s = (s + 1) & cw.cap_mask) {
+      if (cw.mstate[s] == 0u) break;  // (no push runs beside a restore: no position is being claimed)
+      if (cw.mkey[s] == key) {
+        found = true;
+        break;
+      }
+    }
+    atomicAdd(&res[found ? 0 : 1], 1);
+  }
+}
+// second pass, one thread per list (a list has at most wl - 1 elements that count): the key's slot through the
+// push's publication protocol, then its key group, count and ring.  A list of L elements with trigger count t becomes
+// cnt = L + ((t - L) mod slide) elements, its last min(L, wl - 1) numbered up to cnt
+__global__ __launch_bounds__(256) void k_cnt_restore_apply(DevCount cw, int32_t kg, CountStateCols src,
+                                                           const int64_t* __restrict__ eoff, int64_t n, Status* st) {
+  const int64_t ring = cw.wl - 1;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t t = src.trigger_count[i], L = src.n_elems[i];
+    if (L == 0 && t == 0) continue;
+    const int32_t slot = cnt_slot(cw, src.key[i], st, [&] { return kg; });
+    if (slot < 0) continue;  // (cannot happen: the check counted the slots)
+    const int64_t cnt = L + (((t - L) % cw.slide) + cw.slide) % cw.slide;
+    cw.cnt[slot] = cnt;
+    const int64_t m = min(L, ring), e0 = eoff[i] + L - m;
+    for (int64_t j = 0; j < m; j++) {
+      const int64_t q = cnt - (m - 1 - j);  // element j of the kept ones, oldest first
+      const int64_t r = (int64_t)slot * ring + (q - 1) % ring;
+      cw.ring_v[r] = src.val[e0 + j];
+      cw.ring_o[r] = src.ordinal[e0 + j];
+    }
   }
 }
 
@@ -8395,14 +8499,39 @@ size_t count_sort_bytes(int64_t n) {
   (void)rocprim::radix_sort_pairs(nullptr, a, ks, vs, (size_t)n, 0, 32);
   return a;
 }
-void launch_count(const DevCfg& c, DevCount& cw, const int64_t* key, const int64_t* val, int64_t n, DevRows out,
-                  Status* st, hipStream_t s) {
+void launch_count_snapshot_counts(const DevCount& cw, int32_t kg, uint32_t* nl, uint32_t* ne, uint32_t* scan_tmp,
+                                  hipStream_t s) {
+  const int64_t m = (int64_t)cw.cap_mask + 2;
+  const unsigned grid = (unsigned)std::min<int64_t>(8192, (m + 255) / 256);
+  hipLaunchKernelGGL(k_cnt_snap_count, dim3(grid), dim3(256), 0, s, cw, kg, nl, ne);
+  launch_scan(nl, m, scan_tmp, s);
+  launch_scan(ne, m, scan_tmp, s);
+}
+void launch_count_snapshot_rows(const DevCount& cw, const uint32_t* nl, const uint32_t* ne, CountStateCols dst,
+                                hipStream_t s) {
+  const int64_t cap = (int64_t)cw.cap_mask + 1;
+  hipLaunchKernelGGL(k_cnt_snap_rows, dim3((unsigned)std::min<int64_t>(8192, (cap + 255) / 256)), dim3(256), 0, s, cw,
+                     nl, ne, dst);
+}
+void launch_count_restore_check(const DevCount& cw, CountStateCols src, int64_t n, int32_t* res, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_cnt_restore_check, dim3((unsigned)std::min<int64_t>(8192, (n + 255) / 256)), dim3(256), 0, s, cw,
+                     src, n, res);
+}
+void launch_count_restore_apply(const DevCount& cw, int32_t kg, CountStateCols src, const int64_t* eoff, int64_t n,
+                                Status* st, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_cnt_restore_apply, dim3((unsigned)std::min<int64_t>(8192, (n + 255) / 256)), dim3(256), 0, s, cw,
+                     kg, src, eoff, n, st);
+}
+void launch_count(const DevCfg& c, DevCount& cw, const int64_t* key, const int64_t* val, const int32_t* kh, int64_t n,
+                  DevRows out, Status* st, hipStream_t s) {
   if (n <= 0) return;
   const uint32_t none = (uint32_t)cw.max_keys;
   unsigned bits = 1;
   while (((int64_t)1 << bits) <= cw.max_keys) bits++;
   const unsigned grid = (unsigned)std::min<int64_t>(8192, (n + 255) / 256);
-  hipLaunchKernelGGL(k_cnt_slots, dim3(grid), dim3(256), 0, s, cw, key, n, none, st);
+  hipLaunchKernelGGL(k_cnt_slots, dim3(grid), dim3(256), 0, s, cw, key, kh, c.key_kind, c.max_par, n, none, st);
   rocprim::double_buffer<uint32_t> ks(cw.sk[0], cw.sk[1]), vs(cw.sv[0], cw.sv[1]);
   size_t bytes = cw.tmp_bytes;
   (void)rocprim::radix_sort_pairs(cw.tmp, bytes, ks, vs, (size_t)n, 0, bits, s);  // stable: arrival order per key

@@ -431,6 +431,15 @@ struct DevCount {
   size_t tmp_bytes;
   int32_t* sbeg;        // [max_keys] the key's run in the sorted batch
   int32_t* send;
+  int32_t* mkg;         // [max_keys] the key's key group, written by the lane that claims the slot (with
+                        // FW_KEY_HASHED it cannot be recomputed from the key); read by the snapshot only.  Last, so
+                        // that the push kernels read every other field where they did before it was added
+};
+
+// columns of a count-window key group's lists and their elements (fw_list_state, device side)
+struct CountStateCols {
+  int64_t *key, *start, *end, *trigger_count, *timer, *n_elems;  // per list
+  int64_t *ts, *val, *ordinal;                                   // elements
 };
 
 // columns of keyed-state snapshot rows (fw_state_rows, device side)
@@ -512,10 +521,26 @@ void launch_row_update(const DevCfg& c, const PRec* part, const uint32_t* offs, 
 void launch_td_relink(const DevCfg& c, DevTable tb, hipStream_t s);
 void launch_tdigest(const DevCfg& c, const PRec* part, const uint32_t* offs, int32_t T, int64_t n, DevTable tb,
                     TdBuf& td, Status* st, hipStream_t_ s);
-// FW_COUNT: one batch of count windows (key slots, stable sort by key, fire, ring update); val = the push's values
-void launch_count(const DevCfg& c, DevCount& cw, const int64_t* key, const int64_t* val, int64_t n, DevRows out,
-                  Status* st, hipStream_t_ s);
+// FW_COUNT: one batch of count windows (key slots, stable sort by key, fire, ring update); val = the push's values;
+// kh = the push's key hashes (FW_KEY_HASHED), read for the key group of a key's first record only
+void launch_count(const DevCfg& c, DevCount& cw, const int64_t* key, const int64_t* val, const int32_t* kh, int64_t n,
+                  DevRows out, Status* st, hipStream_t_ s);
 size_t count_sort_bytes(int64_t n);
+// FW_COUNT keyed state of one key group in the list operator's logical form (fw_list_state, flink_window.h
+// fw_count_snapshot_key_group).  Pass 1: per position s of the key map, nl[s] = 1 if its key is a list of the key
+// group and ne[s] = the list's elements, then both scanned in place over cap + 1 words, so nl[cap] / ne[cap] are the
+// totals (scan_tmp: launch_scan's).  Pass 2: list nl[s]'s columns and its elements at ne[s] .. in element-number
+// order.
+void launch_count_snapshot_counts(const DevCount& cw, int32_t kg, uint32_t* nl, uint32_t* ne, uint32_t* scan_tmp,
+                                  hipStream_t_ s);
+void launch_count_snapshot_rows(const DevCount& cw, const uint32_t* nl, const uint32_t* ne, CountStateCols dst,
+                                hipStream_t_ s);
+// restore of n lists whose columns the host has checked (eoff[i] = index of list i's first element): the check
+// changes nothing and counts into res[0] the lists whose key is in the map already, into res[1] those that need a
+// slot; the apply claims the slots (as a push does) and writes key group, count and ring
+void launch_count_restore_check(const DevCount& cw, CountStateCols src, int64_t n, int32_t* res, hipStream_t_ s);
+void launch_count_restore_apply(const DevCount& cw, int32_t kg, CountStateCols src, const int64_t* eoff, int64_t n,
+                                Status* st, hipStream_t_ s);
 void launch_rehash(const DevCfg& old_c, DevTable old_t, const DevCfg& new_c, DevTable new_t, hipStream_t_ s);
 void launch_table_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t_ s);
 void launch_reset_regions(const DevCfg& c, DevTable tb, hipStream_t_ s);

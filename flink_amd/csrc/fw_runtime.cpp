@@ -26,6 +26,7 @@
 #include <cstring>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/flink_window.h"
@@ -683,7 +684,7 @@ int maybe_restart_rows(fw_op* op) {
 }
 
 // FW_COUNT: count windows fire while the batch is processed; no state table, timers or suspension
-int push_count(fw_op* op, const int64_t* key, const int64_t* val, int64_t n) {
+int push_count(fw_op* op, const int64_t* key, const int64_t* val, const int32_t* kh, int64_t n) {
   int rc;
   if ((rc = settle(op)) || (rc = maybe_restart_rows(op))) return rc;
   const int64_t rows = (int64_t)op->h_status->out_rows;
@@ -693,7 +694,7 @@ int push_count(fw_op* op, const int64_t* key, const int64_t* val, int64_t n) {
     return rc;
   DevCfg c = op->dc;
   c.ord_base = op->records_in;
-  fwdev::launch_count(c, op->cw, key, val, n, op->out, op->d_status, op->stream);
+  fwdev::launch_count(c, op->cw, key, val, kh, n, op->out, op->d_status, op->stream);
   HIP_OR_RETURN(op, hipGetLastError());
   op->records_in += n;
   op->push_unsettled = true;
@@ -752,7 +753,7 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
   if ((op->dc.agg == FW_AGG_ROW) != (rin != nullptr))
     return set_err(op, FW_ERR_ARG, rin ? "fw_push_row_batch needs an FW_AGG_ROW operator"
                                        : "an FW_AGG_ROW operator takes its records through fw_push_row_batch");
-  if (op->cfg.assigner == FW_COUNT) return push_count(op, key, val, n);
+  if (op->cfg.assigner == FW_COUNT) return push_count(op, key, val, kh, n);
   int rc;
   DevCfg c = op->dc;  // by value: a session batch stamps its taint epoch into it
   // queue the batch-only kernels before waiting for the previous sequence, except with side
@@ -1403,6 +1404,7 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
     HIP_OR_RETURN(op, hipMemsetAsync(w.nslots, 0, sizeof(int32_t), op->stream));
     HIP_OR_RETURN(op, dmalloc(&w.cnt, (size_t)w.max_keys));
     HIP_OR_RETURN(op, hipMemsetAsync(w.cnt, 0, (size_t)w.max_keys * sizeof(int64_t), op->stream));
+    HIP_OR_RETURN(op, dmalloc(&w.mkg, (size_t)w.max_keys));
     const size_t ring = (size_t)w.max_keys * (size_t)std::max<int64_t>(1, w.wl - 1);
     if (ring * 16 > (size_t(64) << 30))
       return set_err(op, FW_ERR_CAPACITY, "count windows: expected_entries * (window length - 1) * 16 B exceeds 64 GiB");
@@ -1503,6 +1505,7 @@ void fw_destroy(fw_op* op) {
     dfree(w.mslot);
     dfree(w.nslots);
     dfree(w.cnt);
+    dfree(w.mkg);
     dfree(w.ring_v);
     dfree(w.ring_o);
     for (int b = 0; b < 2; b++) {
@@ -2067,6 +2070,24 @@ int alloc_state_cols(fw_op* op, StateCols& c, int64_t n) {
   for (int i = 0; i < 8; i++) HIP_OR_RETURN(op, dmalloc(cols[i], (size_t)std::max<int64_t>(n, 1)));
   return FW_OK;
 }
+// KeyGroupRangeAssignment.computeKeyGroupForKeyHash on the host: MathUtils.murmurHash(hash) % maxParallelism
+// (MathUtils.java:134-154; the device's is fw_jmath.h key_group)
+int32_t host_key_group(int32_t hash, int32_t max_par) {
+  uint32_t c = (uint32_t)hash;
+  c *= 0xcc9e2d51u;
+  c = (c << 15) | (c >> 17);
+  c *= 0x1b873593u;
+  c = (c << 13) | (c >> 19);
+  c = c * 5u + 0xe6546b64u;
+  c ^= 4u;
+  c ^= c >> 16;
+  c *= 0x85ebca6bu;
+  c ^= c >> 13;
+  c *= 0xc2b2ae35u;
+  c ^= c >> 16;
+  const int32_t r = (int32_t)c;
+  return (r >= 0 ? r : (r != INT32_MIN ? -r : 0)) % max_par;
+}
 void free_state_cols(StateCols& c) {
   int64_t** cols[8] = {&c.key, &c.start, &c.end, &c.cnt, &c.sum, &c.mn, &c.mx, &c.timer};
   for (int i = 0; i < 8; i++) dfree(*cols[i]);
@@ -2343,6 +2364,151 @@ int fw_restore_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* src,
   if (op->h_status->flags & FW_STATUS_STATE_LOST) return set_err(op, FW_ERR_CAPACITY, "restore: region full");
   const int64_t rows = (int64_t)op->h_status->out_rows;
   return ensure_out_capacity(op, rows + op->table_slots, rows);  // a watermark may fire every restored window
+}
+
+// ---- count windows: keyed state per key group as lists (see flink_window.h)
+int fw_count_snapshot_key_group(fw_op* op, int32_t kg, const fw_list_state* dst, int64_t cap_lists, int64_t cap_elems,
+                                int64_t* n_lists, int64_t* n_elems) {
+  if (!op) return FW_ERR_ARG;
+  if (op->cfg.assigner != FW_COUNT)
+    return set_err(op, FW_ERR_UNSUPPORTED, "fw_count_snapshot_key_group needs an FW_COUNT operator "
+                                           "(other operators: fw_snapshot_key_group)");
+  HIP_OR_RETURN(op, hipSetDevice(op->device));
+  int rc;
+  if ((rc = kg_check(op, kg)) || (rc = settle(op))) return rc;
+  const DevCount& w = op->cw;
+  const int64_t cap = (int64_t)w.cap_mask + 1, m = cap + 1;
+  if ((int64_t)w.max_keys * std::max<int64_t>(1, w.wl - 1) > (int64_t)UINT32_MAX)
+    return set_err(op, FW_ERR_CAPACITY, "count windows: a snapshot numbers at most 2^32 - 1 ring elements "
+                                        "(expected_entries * (window length - 1))");
+  uint32_t *nl = nullptr, *ne = nullptr, *tmp = nullptr;
+  CountStateCols d{};
+  int64_t** cols[9] = {&d.key, &d.start, &d.end, &d.trigger_count, &d.timer, &d.n_elems, &d.ts, &d.val, &d.ordinal};
+  auto done = [&](int code) {
+    dfree(nl);
+    dfree(ne);
+    dfree(tmp);
+    for (int64_t** c : cols) dfree(*c);
+    return code;
+  };
+  if (dmalloc(&nl, (size_t)m) != hipSuccess || dmalloc(&ne, (size_t)m) != hipSuccess ||
+      dmalloc(&tmp, (size_t)(m / 4096 + 2)) != hipSuccess)
+    return done(set_err(op, FW_ERR_HIP, "snapshot: allocation failed"));
+  fwdev::launch_count_snapshot_counts(w, kg, nl, ne, tmp, op->stream);
+  uint32_t got[2] = {0, 0};
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(&got[0], nl + cap, sizeof(uint32_t), hipMemcpyDeviceToHost, op->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&got[1], ne + cap, sizeof(uint32_t), hipMemcpyDeviceToHost, op->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(op->stream);
+  if (e != hipSuccess) return done(set_err(op, FW_ERR_HIP, "snapshot: %s", hipGetErrorString(e)));
+  if (n_lists) *n_lists = got[0];
+  if (n_elems) *n_elems = got[1];
+  if (!dst || (int64_t)got[0] > cap_lists || (int64_t)got[1] > cap_elems || got[0] == 0) return done(FW_OK);
+  for (int i = 0; i < 9; i++)
+    if (dmalloc(cols[i], (size_t)(i < 6 ? got[0] : got[1])) != hipSuccess)
+      return done(set_err(op, FW_ERR_HIP, "snapshot: allocation failed"));
+  fwdev::launch_count_snapshot_rows(w, nl, ne, d, op->stream);
+  e = hipGetLastError();
+  int64_t* hs[9] = {dst->key, dst->start, dst->end, dst->trigger_count, dst->timer, dst->n_elems,
+                    dst->ts,  dst->val,   dst->ordinal};
+  for (int i = 0; i < 9 && e == hipSuccess; i++) {
+    const size_t cnt = i < 6 ? got[0] : got[1];
+    if (hs[i] && cnt) e = hipMemcpyAsync(hs[i], *cols[i], cnt * sizeof(int64_t), hipMemcpyDeviceToHost, op->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(op->stream);
+  if (e != hipSuccess) return done(set_err(op, FW_ERR_HIP, "snapshot: %s", hipGetErrorString(e)));
+  return done(FW_OK);
+}
+
+int fw_count_restore_key_group(fw_op* op, int32_t kg, const fw_list_state* src, int64_t n_lists, int64_t n_elems) {
+  if (!op || n_lists < 0 || n_elems < 0 || (n_lists > 0 && !src))
+    return op ? set_err(op, FW_ERR_ARG, "invalid arguments") : FW_ERR_ARG;
+  if (op->cfg.assigner != FW_COUNT)
+    return set_err(op, FW_ERR_UNSUPPORTED, "fw_count_restore_key_group needs an FW_COUNT operator "
+                                           "(other operators: fw_restore_key_group)");
+  HIP_OR_RETURN(op, hipSetDevice(op->device));
+  int rc;
+  if ((rc = kg_check(op, kg)) || (rc = settle(op))) return rc;
+  if (n_lists == 0)
+    return n_elems == 0 ? FW_OK : set_err(op, FW_ERR_ARG, "list lengths do not add up to n_elems");
+  if (!src->key || !src->start || !src->end || !src->trigger_count || !src->n_elems ||
+      (n_elems > 0 && (!src->val || !src->ordinal)))
+    return set_err(op, FW_ERR_ARG, "null state column");
+  // the lists' own columns, on the host: nothing has changed when one of them is refused
+  DevCount& w = op->cw;
+  std::vector<int64_t> eoff((size_t)n_lists);
+  std::unordered_set<int64_t> seen;
+  seen.reserve((size_t)n_lists);
+  int64_t total = 0;
+  for (int64_t i = 0; i < n_lists; i++) {
+    const int64_t L = src->n_elems[i], t = src->trigger_count[i], k = src->key[i];
+    if (L < 0) return set_err(op, FW_ERR_ARG, "list %lld: negative list length", (long long)i);
+    if (t < 0 || t >= w.slide)
+      return set_err(op, FW_ERR_ARG, "list %lld: trigger count %lld is not in [0, %lld) (CountTrigger.of(slide) clears "
+                                     "its count at each firing)", (long long)i, (long long)t, (long long)w.slide);
+    if (src->start[i] != INT64_MIN || src->end[i] != INT64_MAX)
+      return set_err(op, FW_ERR_ARG, "list %lld: window [%lld, %lld) is not the GlobalWindow", (long long)i,
+                     (long long)src->start[i], (long long)src->end[i]);
+    if (L > n_elems - total) return set_err(op, FW_ERR_ARG, "list lengths do not add up to n_elems");
+    eoff[(size_t)i] = total;
+    total += L;
+    if (op->cfg.key_kind != FW_KEY_HASHED) {  // (a hashed key's key group is the caller's word)
+      const int32_t h = op->cfg.key_kind == FW_KEY_INT ? (int32_t)k : (int32_t)(k ^ (int64_t)((uint64_t)k >> 32));
+      if (host_key_group(h, op->cfg.max_parallelism) != kg)
+        return set_err(op, FW_ERR_KEY_GROUP, "key %lld is not in key group %d", (long long)k, kg);
+    }
+    if (!seen.insert(k).second)
+      return set_err(op, FW_ERR_STATE, "key %lld is restored twice (a count window's key has one list)", (long long)k);
+  }
+  if (total != n_elems) return set_err(op, FW_ERR_ARG, "list lengths do not add up to n_elems");
+  int64_t max_ord = -1;
+  for (int64_t i = 0; i < n_elems; i++) max_ord = std::max(max_ord, src->ordinal[i]);
+  CountStateCols d{};
+  int64_t* d_eoff = nullptr;
+  int32_t* res = nullptr;
+  auto done = [&](int code) {
+    for (int64_t** c : {&d.key, &d.trigger_count, &d.n_elems, &d.val, &d.ordinal, &d_eoff}) dfree(*c);
+    dfree(res);
+    return code;
+  };
+  struct Col {
+    int64_t** dev;
+    const int64_t* host;
+    int64_t n;
+  };
+  const Col cols[6] = {{&d.key, src->key, n_lists},         {&d.trigger_count, src->trigger_count, n_lists},
+                       {&d.n_elems, src->n_elems, n_lists}, {&d_eoff, eoff.data(), n_lists},
+                       {&d.val, src->val, n_elems},         {&d.ordinal, src->ordinal, n_elems}};
+  for (const Col& c : cols) {
+    if (dmalloc(c.dev, (size_t)c.n) != hipSuccess) return done(set_err(op, FW_ERR_HIP, "restore: allocation failed"));
+    if (c.n && hipMemcpyAsync(*c.dev, c.host, (size_t)c.n * sizeof(int64_t), hipMemcpyHostToDevice, op->stream) != hipSuccess)
+      return done(set_err(op, FW_ERR_HIP, "restore: copy failed"));
+  }
+  if (dmalloc(&res, 2) != hipSuccess || hipMemsetAsync(res, 0, 2 * sizeof(int32_t), op->stream) != hipSuccess)
+    return done(set_err(op, FW_ERR_HIP, "restore: allocation failed"));
+  // first pass: keys already present, and the slots the new ones need against the pool
+  fwdev::launch_count_restore_check(w, d, n_lists, res, op->stream);
+  int32_t hres[2] = {0, 0}, nslots = 0;
+  if (hipGetLastError() != hipSuccess ||
+      hipMemcpyAsync(hres, res, sizeof hres, hipMemcpyDeviceToHost, op->stream) != hipSuccess ||
+      hipMemcpyAsync(&nslots, w.nslots, sizeof nslots, hipMemcpyDeviceToHost, op->stream) != hipSuccess ||
+      hipStreamSynchronize(op->stream) != hipSuccess)
+    return done(set_err(op, FW_ERR_HIP, "restore: check kernel failed"));
+  if (hres[0])
+    return done(set_err(op, FW_ERR_STATE, "%d restored key(s) already have count-window state in this operator",
+                        hres[0]));
+  if ((int64_t)nslots + hres[1] > w.max_keys)
+    return done(set_err(op, FW_ERR_CAPACITY, "restore: %d new keys do not fit the %d key slots (%d taken; raise "
+                                             "expected_entries)", hres[1], w.max_keys, std::min(nslots, w.max_keys)));
+  fwdev::launch_count_restore_apply(w, kg, d, d_eoff, n_lists, op->d_status, op->stream);
+  const bool launched = hipGetLastError() == hipSuccess;
+  rc = sync_status(op);
+  if (!launched || rc) return done(rc ? rc : set_err(op, FW_ERR_HIP, "restore kernel failed"));
+  done(FW_OK);
+  if (op->h_status->flags & FW_STATUS_STATE_LOST) return set_err(op, FW_ERR_CAPACITY, "restore: key map full");
+  // later pushes are numbered after every restored element, as the reduce aggregates' restore does
+  op->records_in = std::max(op->records_in, max_ord + 1);
+  return FW_OK;
 }
 
 int fw_key_groups_device(const int64_t* key, const int32_t* key_hash, int32_t key_kind, int64_t n,

@@ -20,15 +20,13 @@ import numpy as np
 
 from . import _native as N
 from .keygroups import KeyGroupRange
-from .operator import _KEY_KINDS, _is_torch
+from .operator import ELEM_DTYPE, LIST_STATE_DTYPE, _KEY_KINDS, _is_torch  # (the two dtypes: one definition)
 from .windowing import (VALUE_TYPES, ContinuousEventTimeTrigger, CountTrigger, EventTimeTrigger, Evictor, Trigger,
                         WindowAssigner)
 
 LIST_ROW_FIELDS = ("key", "start", "end", "count", "sum", "min", "max", "first", "elem_off")
 LIST_ROW_DTYPE = np.dtype([(f, "<i8") for f in LIST_ROW_FIELDS] + [("epoch", "<i8")])
-ELEM_DTYPE = np.dtype([("ts", "<i8"), ("val", "<i8"), ("ordinal", "<i8")])
 SIDE_DTYPE = np.dtype([("key", "<i8"), ("ts", "<i8"), ("val", "<i8"), ("epoch", "<i8")])
-LIST_STATE_DTYPE = np.dtype([(f, "<i8") for f in ("key", "start", "end", "trigger_count", "timer", "n_elems")])
 
 
 class GpuListWindowOperator:

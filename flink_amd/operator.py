@@ -24,6 +24,10 @@ ROW_DTYPE = np.dtype([(f, "<i8") for f in ROW_FIELDS] + [("epoch", "<i8")])
 STATE_FIELDS = ("key", "start", "end", "count", "sum", "min", "max", "timer")
 STATE_DTYPE = np.dtype([(f, "<i8") for f in STATE_FIELDS])
 SIDE_DTYPE = np.dtype([("key", "<i8"), ("ts", "<i8"), ("val", "<i8"), ("epoch", "<i8")])
+# list state per key group (fw_list_state): the lists and their elements concatenated in list order.  Snapshots of
+# GpuListWindowOperator (listwindow.py takes the two from here) and of a count-window GpuWindowOperator
+LIST_STATE_DTYPE = np.dtype([(f, "<i8") for f in ("key", "start", "end", "trigger_count", "timer", "n_elems")])
+ELEM_DTYPE = np.dtype([("ts", "<i8"), ("val", "<i8"), ("ordinal", "<i8")])
 
 _KEY_KINDS = {"long": N.FW_KEY_LONG, "int": N.FW_KEY_INT, "hashed": N.FW_KEY_HASHED}
 
@@ -89,6 +93,7 @@ class GpuWindowOperator:
         self.key_group_range = kgr
         self.max_parallelism = max_parallelism
         self.device = device
+        self._count = c.assigner == N.FW_COUNT  # count windows: list state (snapshot_key_group)
         self._cfg = c
         self._h = ctypes.c_void_p()
         L = N.lib()
@@ -501,8 +506,27 @@ class GpuWindowOperator:
         return STATE_DTYPE if bb == 0 else np.dtype(STATE_DTYPE.descr + [("acc", "u1", (bb,))])
 
     def snapshot_key_group(self, kg):
-        """Live (key, window) accumulators of key group kg as a state_dtype() array (no order)."""
+        """Live (key, window) accumulators of key group kg as a state_dtype() array (no order).  Count windows:
+        (lists LIST_STATE_DTYPE, elements ELEM_DTYPE concatenated in list order), each key's trigger count and the
+        last elements a later firing can read (fw_count_snapshot_key_group) -- the form GpuListWindowOperator
+        snapshots and restores."""
         L = N.lib()
+        if self._count:
+            nl, ne = ctypes.c_int64(), ctypes.c_int64()
+            N.check(L.fw_count_snapshot_key_group(self._h, int(kg), None, 0, 0, ctypes.byref(nl), ctypes.byref(ne)),
+                    self._h)
+            lc = {f: np.zeros(nl.value, dtype=np.int64) for f in LIST_STATE_DTYPE.names}
+            ec = {f: np.zeros(ne.value, dtype=np.int64) for f in ELEM_DTYPE.names}
+            st = N.FwListState(**{f: lc[f].ctypes.data for f in lc}, **{f: ec[f].ctypes.data for f in ec})
+            N.check(L.fw_count_snapshot_key_group(self._h, int(kg), ctypes.byref(st), nl.value, ne.value,
+                                                  ctypes.byref(nl), ctypes.byref(ne)), self._h)
+            lists = np.zeros(nl.value, dtype=LIST_STATE_DTYPE)
+            for f in lc:
+                lists[f] = lc[f]
+            el = np.zeros(ne.value, dtype=ELEM_DTYPE)
+            for f in ec:
+                el[f] = ec[f]
+            return lists, el
         bb = L.fw_state_block_bytes(self._h)
         n = ctypes.c_int64()
         N.check(L.fw_snapshot_key_group_blocks(self._h, int(kg), None, None, 0, ctypes.byref(n)), self._h)
@@ -520,11 +544,25 @@ class GpuWindowOperator:
         return out
 
     def snapshot_state(self):
-        """{key group: state_dtype() rows} for every key group of this operator's KeyGroupRange."""
+        """{key group: state_dtype() rows} for every key group of this operator's KeyGroupRange (count windows:
+        {key group: (lists, elements)})."""
         return {kg: self.snapshot_key_group(kg) for kg in self.key_group_range}
 
-    def restore_key_group(self, kg, rows):
+    def restore_key_group(self, kg, rows, elems=None):
+        """Restores snapshot_key_group's rows of key group kg.  Count windows: restore_key_group(kg, lists, elems),
+        the pair a count-window snapshot or the equivalent GpuListWindowOperator's returned."""
         L = N.lib()
+        if self._count:
+            lists = np.ascontiguousarray(rows, dtype=LIST_STATE_DTYPE)
+            elems = np.ascontiguousarray(elems if elems is not None else np.zeros(0, dtype=ELEM_DTYPE),
+                                         dtype=ELEM_DTYPE)
+            lc = {f: np.ascontiguousarray(lists[f]) for f in LIST_STATE_DTYPE.names}
+            ec = {f: np.ascontiguousarray(elems[f]) for f in ELEM_DTYPE.names}
+            st = N.FwListState(**{f: lc[f].ctypes.data for f in lc}, **{f: ec[f].ctypes.data for f in ec})
+            N.check(L.fw_count_restore_key_group(self._h, int(kg), ctypes.byref(st), len(lists), len(elems)), self._h)
+            return
+        if elems is not None:
+            raise ValueError("only count windows restore (lists, elems); this operator restores state_dtype() rows")
         bb = L.fw_state_block_bytes(self._h)
         rows = np.ascontiguousarray(rows)
         if bb and (rows.dtype.names is None or "acc" not in rows.dtype.names or rows.dtype["acc"].shape != (bb,)):
@@ -539,7 +577,13 @@ class GpuWindowOperator:
         """Restores the key groups of `snapshot` ({kg: rows}) that this operator owns; others are skipped,
         as a subtask reads only the key groups of its own KeyGroupRange."""
         for kg, rows in snapshot.items():
-            if kg in self.key_group_range and len(rows):
+            if kg not in self.key_group_range:
+                continue
+            if self._count:
+                lists, elems = rows
+                if len(lists):
+                    self.restore_key_group(kg, lists, elems)
+            elif len(rows):
                 self.restore_key_group(kg, rows)
 
     snapshotState, initializeState = snapshot_state, initialize_state

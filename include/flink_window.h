@@ -658,6 +658,39 @@ int fw_list_snapshot_key_group(fw_list* op, int32_t key_group, const fw_list_sta
 int fw_list_restore_key_group(fw_list* op, int32_t key_group, const fw_list_state* src, int64_t n_lists,
                               int64_t n_elems);
 
+/* Count windows (an fw_op with FW_COUNT): the keyed state of one key group, in the logical form of the list operator
+ * above, so it moves between count handles of any parallelism and to and from the equivalent fw_list handle
+ * (FW_GLOBAL, FW_TRIGGER_COUNT with trigger_count = slide, FW_EVICT_COUNT with evict_count = size and the same
+ * evict_after).  Conventions as fw_list_snapshot_key_group / fw_list_restore_key_group: dst NULL or too small a
+ * capacity returns only the counts; the elements of all lists are concatenated in list order; lists come out in no
+ * particular order; both calls settle an unsettled device push first.  A handle that is not FW_COUNT returns
+ * FW_ERR_UNSUPPORTED, a key group outside the handle's KeyGroupRange FW_ERR_KEY_GROUP.  A key's key group is the one
+ * of its first record (of its key_hash with FW_KEY_HASHED); count pushes do not check the KeyGroupRange, and a key
+ * outside it appears in no snapshot.
+ *
+ * A snapshot row is the state EvictingWindowOperator holds for the key after its k elements, reduced to what a later
+ * firing can still read (EvictingWindowOperator.java:334-366, CountTrigger.java:47-70, CountEvictor.java:63-78):
+ *   start = Long.MIN_VALUE, end = Long.MAX_VALUE, timer = 0 (GlobalWindows have no timers);
+ *   trigger_count = k % slide (CountTrigger clears its count at each firing);
+ *   the reference's list has L_ref = k elements while nothing has fired (f = k - k % slide == 0), else
+ *   min(size, f) + (k - f); the row carries its last m = min(L_ref, wl - 1) elements, oldest first, with their values
+ *   and arrival ordinals (wl = size, or size + slide when evicting after).  Older elements of the list are ones the
+ *   next firing evicts before the function sees them.  Every ts is Long.MIN_VALUE: count handles keep no timestamps,
+ *   and CountEvictor and GlobalWindow rows read none;
+ *   a key with m == 0 and trigger_count == 0 is omitted; with m == 0 and trigger_count != 0 its list is empty.
+ * A restore takes lists in this form, or the full lists of the equivalent list operator's snapshot.  A list of L
+ * elements with trigger count t becomes a key of cnt = L + ((t - L) mod slide) elements (non-negative mod: L when the
+ * residues agree), whose ring takes the list's last min(L, wl - 1) elements: element i from the end is element number
+ * cnt - i.  Refused before anything changes: t outside [0, slide), a negative n_elems, a window that is not the
+ * GlobalWindow or list lengths that do not add up to n_elems (FW_ERR_ARG); a key of FW_KEY_LONG / FW_KEY_INT that is
+ * not in key_group (FW_ERR_KEY_GROUP); a key that occurs twice or already has state in the handle (FW_ERR_STATE);
+ * more new keys than the handle's key slots have left (FW_ERR_CAPACITY).  Later pushes are numbered after the largest
+ * restored ordinal.  fw_snapshot_key_group(_blocks) / fw_restore_key_group(_blocks) keep refusing count handles. */
+int fw_count_snapshot_key_group(fw_op* op, int32_t key_group, const fw_list_state* dst, int64_t cap_lists,
+                                int64_t cap_elems, int64_t* n_lists, int64_t* n_elems);
+int fw_count_restore_key_group(fw_op* op, int32_t key_group, const fw_list_state* src, int64_t n_lists,
+                               int64_t n_elems);
+
 /* Synthetic source used by the benchmarks (the same counter-based generator as the CPU
  * baseline and the tests): record i of stream `seed` has
  *   key = splitmix64(seed ^ 4i) mod num_keys  (uniform)  or Zipf(zipf_s) over num_keys,
