@@ -102,7 +102,8 @@ __device__ __forceinline__ void compact_decode(const DevCfg& c, int32_t p, int64
 // ---- narrow records (DevCfg::narrow; dense single-pass batches): 8 bytes, {key << 35 | (d - ndn0) << 32 | (u32)value}
 // for a key in [-2^28, 2^28), a window delta d (compact_delta) in [ndn0, ndn0 + 8) and an int32 value.  The
 // aggregate widens a narrow record back to its CRec in registers (narrow_to_crec), so its LDS table and the region
-// entries are those of the compact form.
+// entries are those of the compact form; a batch's first launch (k_dn_aggregate) keys its table by the record's
+// upper half instead.
 constexpr int NW_DBITS = 3;
 __device__ __forceinline__ bool narrow_encode(const DevCfg& c, int64_t key, int64_t d, int64_t v, uint64_t* w) {
   const int64_t dn = d - c.ndn0;
@@ -7252,6 +7253,8 @@ __global__ __launch_bounds__(FW_FIRE_THREADS) void k_table_stats(DevCfg c, DevTa
 //                   accumulators: combining, restore), and writes every group densely into the region's other buffer
 //                   (whole 64-byte entries, coalesced); a region is committed (buffer flipped) only when all of its
 //                   groups are written, so a suspended launch resumes by redoing the regions not yet committed;
+//   k_dn_aggregate  the same for a narrow single-pass batch, with a table keyed by the records' 32-bit ids that holds
+//                   the batch's deltas; the regions it refuses are redone by k_dt_aggregate in a resumed sequence;
 //   k_dt_fire       streams the due regions' entries: windows with maxTimestamp <= wm are emitted
 //                   (WindowOperator.onEventTime, :424-469), the rest are copied into the other buffer.
 // A region whose entries and new groups exceed the LDS table is done in 2^b passes, each over the (key, window)s
@@ -7950,6 +7953,323 @@ __global__ __launch_bounds__(FW_DT_THREADS) void k_dt_aggregate(DevCfg c, const 
   }
 }
 
+// ---- the narrow-keyed table (k_dn_aggregate): the first launch of a narrow single-pass batch.  A narrow record's
+// upper half, key << 3 | (d - ndn0), already names its (key, window) uniquely, and its value is an int32, so the LDS
+// table is keyed by that 32-bit id (buckets of 4: a probe is one 16-byte read) and holds only the batch's delta:
+// acc = count << 48 | sum of the values biased by 2^31 (exact for a run of at most 65535 records: the count fits 16
+// bits, and 65535 (2^32 - 1) < 2^48, so no carry reaches it), mm = {min, max} as int32.  A record costs the bucket
+// read, one 64-bit add, the read of mm and, rarely, a 32-bit min / max.  The region's entries claim their slots
+// without tickets (they are unique and counted: live), keep {slot, id, count, sum} in registers and are written back
+// to their own dense positions; the groups the records claimed follow at live + rank.  A region the table cannot
+// take (see the refusals in the kernel) is left untouched for the resumed sequence's kernels.
+constexpr uint32_t DN_EMPTY = 0xFFFFFFFFu;  // (the id of key -1 in narrow window 7: such a region is refused)
+typedef int32_t i32x2 __attribute__((ext_vector_type(2)));
+template <int NS>
+struct DnLds {
+  alignas(16) uint32_t id[NS];
+  unsigned long long acc[NS];
+  i32x2 mm[NS];  // {min, max}
+};
+struct DnMisc {
+  int fill, refuse, over, nout, capover;  // refuse: by the read-in, over: by the record loop
+  long long ntmin;
+};
+template <int NS>
+__device__ __forceinline__ uint32_t dn_home(uint32_t id) {  // first slot of the id's home bucket
+  uint32_t h = id * 0x9E3779B1u;
+  h ^= h >> 15;
+  return (uint32_t)(((uint64_t)h * (NS / 4)) >> 32) * 4u;
+}
+// find or claim the slot of id from the bucket at slot s0 on (the protocol of dk_slot); TICKET: a claim takes a
+// ticket below the fill limit (the record loop; the read-in's claims are counted beforehand).  -1: table full
+template <int NS, bool TICKET>
+__device__ __forceinline__ int dn_slot(DnLds<NS>& T, DnMisc& M, uint32_t id, uint32_t s0) {
+  constexpr int LIMIT = NS * 15 / 16;
+  for (int guard = 0; guard < NS / 2;) {
+    asm volatile("" ::: "memory");
+    const u32x4 g = *reinterpret_cast<const u32x4*>(&T.id[s0]);
+    if (g.x == id) return (int)s0;
+    if (g.y == id) return (int)s0 + 1;
+    if (g.z == id) return (int)s0 + 2;
+    if (g.w == id) return (int)s0 + 3;
+    const int e = g.x == DN_EMPTY ? 0 : g.y == DN_EMPTY ? 1 : g.z == DN_EMPTY ? 2 : g.w == DN_EMPTY ? 3 : -1;
+    if (e >= 0) {
+      if (TICKET) {
+        if (__hip_atomic_load(&M.fill, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= LIMIT) return -1;
+        if (atomicAdd(&M.fill, 1) >= LIMIT) {
+          atomicSub(&M.fill, 1);
+          return -1;
+        }
+      }
+      const uint32_t o = atomicCAS(&T.id[s0 + e], DN_EMPTY, id);
+      if (o == DN_EMPTY) return (int)s0 + e;  // claimed (acc and mm were initialised with the table)
+      if (TICKET) atomicSub(&M.fill, 1);
+      if (o == id) return (int)s0 + e;
+      continue;  // lost the claim race: re-read the bucket
+    }
+    s0 = s0 + 4 == (uint32_t)NS ? 0u : s0 + 4;
+    guard++;
+  }
+  return -1;
+}
+// one record into slot s
+template <int NS>
+__device__ __forceinline__ void dn_add(DnLds<NS>& T, int s, uint32_t vbits) {
+  atomicAdd(&T.acc[s], (1ull << 48) + (unsigned long long)(vbits ^ 0x80000000u));
+  // (a stale read can only be above the minimum / below the maximum, so skipping is exact: dt_add of DtLdsK)
+  const i32x2 m = T.mm[s];
+  const int32_t v = (int32_t)vbits;
+  int32_t* mp = reinterpret_cast<int32_t*>(&T.mm[s]);
+  if (v < m.x) atomicMin(mp, v);
+  if (v > m.y) atomicMax(mp + 1, v);
+}
+// One workgroup of NT threads per region, a table of NS slots, RPT records and up to EPT region entries per thread.
+// Commits like k_dt_aggregate; a refused region changes nothing, clears prog.done[p] and suspends the push, so the
+// resumed sequence (k_dt_aggregate<DT_RECS, true>, then <DT_RECS, false>) takes it.
+template <int NT, int NS, int RPT, int EPT, int WAVES>
+__global__ __launch_bounds__(NT, WAVES) void k_dn_aggregate(DevCfg c, const uint64_t* __restrict__ nrec, DevTable tb,
+                                                            AggProg prog, Status* st, const uint32_t* __restrict__ rsv,
+                                                            int64_t rcap) {
+  static_assert(NS % 16 == 0 && RPT % 2 == 0, "buckets of 4; narrow records are loaded in pairs");
+  constexpr int LIMIT = NS * 15 / 16;
+  constexpr int ND = FW_DT_NDEPTH > 0 ? FW_DT_NDEPTH : 1;
+  constexpr int64_t RS = (int64_t)NT * RPT;
+  __shared__ DnLds<NS> T;
+  __shared__ DnMisc M;
+  const int32_t p = blockIdx.x;
+  if (p >= c.P) return;
+  const int tid = threadIdx.x, lane = __lane_id();
+  auto refuse = [&](bool counted) {
+    if (tid == 0) {
+      prog.done[p] = 0;
+      atomicOr(&st->suspended, (int)FW_SUSP_AGG);
+      if (counted) atomicAdd(&st->dn_refused, 1);
+    }
+  };
+  // a batch the single pass could not take, or without compact words: the resumed sequence reads its offset form
+  if (rsv[c.P + RSV_OVER] || !c.compact || *c.wide || (c.diag & DIAG_DT_WIDE)) {
+    refuse(false);
+    return;
+  }
+  const int64_t begin = (int64_t)p * 2 * rcap, end = begin + rsv[p];
+  if (begin == end) {  // nothing for this region: it stays as it is
+    if (tid == 0) prog.done[p] = 1;
+    return;
+  }
+  const int32_t live = tb.live[p];
+  // refusals known up front: a run whose count would not fit the packed accumulator, a region in passes, more
+  // entries than the threads hold or the table takes
+  if (end - begin > 65535 || tb.passes[p] != 0 || live > EPT * NT || live > LIMIT) {
+    refuse(true);
+    return;
+  }
+  const int X = tb.cur[p], Y = X ^ 1;
+  const int64_t base = (int64_t)p << c.log_r, R = (int64_t)1 << c.log_r;
+  const Entry* __restrict__ src = tb.ent[X] + base;
+  Entry* __restrict__ dst = tb.ent[Y] + base;
+  // the ring of raw pairs (dt_attempt's): a lane reads its two records of a round with one 16-byte load, branch-free
+  // from an index clamped into the run (which starts at an even record)
+  auto load_raw = [&](i64x2 (&q)[RPT / 2], int64_t r0) {
+#pragma unroll
+    for (int j = 0; j < RPT; j += 2) {
+      int64_t i = r0 + (int64_t)j * NT + 2 * (int64_t)tid;
+      if (i >= end) i = (end - 1) & ~(int64_t)1;
+      q[j / 2] = *reinterpret_cast<const i64x2*>(nrec + i);
+    }
+  };
+  i64x2 rq[ND][RPT / 2];
+  load_raw(rq[0], begin);  // (its latency overlaps the clear and the read-in)
+  for (int h = tid; h < NS; h += NT) {
+    T.id[h] = DN_EMPTY;
+    T.acc[h] = 0ull;
+    T.mm[h] = i32x2{INT32_MAX, INT32_MIN};
+  }
+  if (tid == 0) {
+    M.fill = live;  // the entries are unique: no ticket each
+    M.refuse = 0;
+    M.over = 0;
+    M.nout = 0;
+    M.capover = 0;
+    M.ntmin = LMAX;
+  }
+  __syncthreads();
+  // the region's entries: entry u * NT + tid in this thread's registers, its min / max in its slot
+  int es[EPT];
+  uint32_t eid[EPT];
+  int64_t ecnt[EPT], esum[EPT];
+#pragma unroll
+  for (int u0 = 0; u0 < EPT; u0 += 2) {
+    Entry e[2];
+#pragma unroll
+    for (int v = 0; v < 2; v++) {
+      const int32_t i = (u0 + v) * NT + tid;
+      if (u0 + v < EPT && i < live) e[v] = src[i];
+    }
+#pragma unroll
+    for (int v = 0; v < 2; v++) {
+      if (u0 + v >= EPT) continue;
+      const int u = u0 + v;
+      const int32_t i = u * NT + tid;
+      es[u] = -1;
+      eid[u] = 0;
+      ecnt[u] = esum[u] = 0;
+      if (i >= live) continue;
+      const int64_t d = compact_delta(c, e[v].start), dn = d - c.ndn0;
+      const uint32_t id = (uint32_t)(((uint64_t)e[v].key << NW_DBITS) | (uint64_t)(dn & ((1 << NW_DBITS) - 1)));
+      // an entry without a narrow form (a restored row, a window from before the watermark's): refused
+      if (d < 0 || (uint64_t)dn >= (1ull << NW_DBITS) || e[v].key < -(1ll << 28) || e[v].key >= (1ll << 28) ||
+          e[v].mn != (int64_t)(int32_t)e[v].mn || e[v].mx != (int64_t)(int32_t)e[v].mx || id == DN_EMPTY) {
+        M.refuse = 1;
+        continue;
+      }
+      const int s = dn_slot<NS, false>(T, M, id, dn_home<NS>(id));
+      if (s < 0) {
+        M.refuse = 1;
+        continue;
+      }
+      T.mm[s] = i32x2{(int32_t)e[v].mn, (int32_t)e[v].mx};  // (nobody adds before the barrier)
+      es[u] = s;
+      eid[u] = id;
+      ecnt[u] = e[v].cnt;
+      esum[u] = e[v].sum;
+    }
+  }
+  __syncthreads();
+  if (M.refuse) {
+    refuse(true);
+    return;
+  }
+  // the batch's records: round r0 + d RS sits in rq[d]; once its registers are read, rq[d] takes the round ND later
+  {
+#pragma unroll
+    for (int d = 1; d < ND; d++) load_raw(rq[d], begin + (int64_t)d * RS);
+    bool stop = false;
+    for (int64_t r0 = begin; r0 < end && !stop; r0 += ND * RS) {
+#pragma unroll
+      for (int d = 0; d < ND; d++) {
+        const int64_t rr = r0 + (int64_t)d * RS;
+        if (rr >= end || stop) continue;
+        uint32_t id[RPT], vb[RPT], s0[RPT];
+#pragma unroll
+        for (int j = 0; j < RPT; j += 2) {
+          id[j] = (uint32_t)((uint64_t)rq[d][j / 2].x >> 32), vb[j] = (uint32_t)rq[d][j / 2].x;
+          id[j + 1] = (uint32_t)((uint64_t)rq[d][j / 2].y >> 32), vb[j + 1] = (uint32_t)rq[d][j / 2].y;
+        }
+        if (rr + ND * RS < end) load_raw(rq[d], rr + ND * RS);
+        // every home bucket read before any is used (plain reads: an id, once claimed, never changes, and a stale
+        // EMPTY only sends the record to dn_slot, which re-reads)
+        u32x4 g[RPT];
+#pragma unroll
+        for (int j = 0; j < RPT; j++) {
+          s0[j] = dn_home<NS>(id[j]);
+          g[j] = *reinterpret_cast<const u32x4*>(&T.id[s0[j]]);
+        }
+        uint32_t miss = 0;
+#pragma unroll
+        for (int j = 0; j < RPT; j++) {
+          const int64_t i = rr + (int64_t)(j & ~1) * NT + 2 * (int64_t)tid + (j & 1);
+          if (i >= end) continue;
+          if (id[j] == DN_EMPTY) {  // the EMPTY marker as an id: the region goes to the other kernels
+            M.over = 1;
+            stop = true;
+            continue;
+          }
+          const int q = g[j].x == id[j] ? 0 : g[j].y == id[j] ? 1 : g[j].z == id[j] ? 2 : g[j].w == id[j] ? 3 : -1;
+          if (q >= 0)
+            dn_add(T, (int)s0[j] + q, vb[j]);
+          else
+            miss |= 1u << j;
+        }
+        if (miss && !stop) {
+#pragma unroll
+          for (int j = 0; j < RPT; j++) {
+            if (!(miss >> j & 1) || stop) continue;
+            const int s = dn_slot<NS, true>(T, M, id[j], s0[j]);
+            if (s < 0) {  // the groups exceed the fill limit: passes, in the other kernels
+              M.over = 1;
+              stop = true;
+              continue;
+            }
+            dn_add(T, s, vb[j]);
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (M.over) {
+    refuse(true);
+    return;
+  }
+  // write-back.  The entries keep their dense positions; a thread empties the slots of its own entries, so the
+  // slots still occupied after that are the groups the records claimed
+  auto group = [&](uint32_t id, int s, int64_t cnt, int64_t sum) {
+    const unsigned long long a = T.acc[s];
+    const i32x2 m = T.mm[s];
+    const int64_t dc = (int64_t)(a >> 48);
+    const int64_t ds = (int64_t)(a & ((1ull << 48) - 1)) - (dc << 31);  // the batch's sum, without the bias
+    Entry e;
+    e.key = (int64_t)((int32_t)id >> NW_DBITS);
+    e.start = (int64_t)((uint64_t)c.cbase +
+                        (uint64_t)((int64_t)(id & ((1u << NW_DBITS) - 1)) + c.ndn0) * (uint64_t)c.slide);
+    e.end = jadd(e.start, c.size);
+    e.cnt = cnt + dc;
+    e.sum = (int64_t)((uint64_t)sum + (uint64_t)ds);
+    e.mn = m.x;
+    e.mx = m.y;
+    e.meta = FW_TIMER;  // EventTimeTrigger's timer at maxTimestamp (= the GC timer with lateness 0)
+    return e;
+  };
+  long long nt = LMAX;
+#pragma unroll
+  for (int u = 0; u < EPT; u++) {
+    if (es[u] < 0) continue;
+    const Entry e = group(eid[u], es[u], ecnt[u], esum[u]);
+    dst[u * NT + tid] = e;  // (below live <= R)
+    nt = min(nt, (long long)jsub(e.end, 1));
+    T.id[es[u]] = DN_EMPTY;
+  }
+  const int nnew = M.fill - live;  // (every ticket of the record loop became a claim or was returned)
+  if (nnew > 0) {
+    __syncthreads();
+    for (int h0 = 0; h0 < NS; h0 += NT) {
+      const int h = h0 + tid;
+      const uint32_t id = h < NS ? T.id[h] : DN_EMPTY;
+      const bool g = id != DN_EMPTY;
+      const uint64_t m = __ballot(g);
+      int wb = 0;
+      if (lane == 0 && m) wb = atomicAdd(&M.nout, __popcll(m));
+      wb = __shfl(wb, 0, 64);
+      if (g) {
+        const int64_t pos = (int64_t)live + wb + __popcll(m & lanemask_lt());
+        const Entry e = group(id, h, 0, 0);
+        if (pos < R)
+          dst[pos] = e;
+        else
+          M.capover = 1;
+        nt = min(nt, (long long)jsub(e.end, 1));
+      }
+    }
+  }
+  if (nt != LMAX) atomicMin(&M.ntmin, nt);
+  __syncthreads();
+  if (tid == 0) {
+    const long long out = (long long)live + M.nout;
+    if (M.capover) {  // the region's buffers are too small: nothing committed, the host grows them and resumes
+      atomicMax(&st->need_live, (int)min(out, (long long)INT32_MAX));
+      prog.done[p] = 0;
+      atomicOr(&st->suspended, (int)FW_SUSP_AGG);
+    } else {
+      tb.cur[p] = (uint8_t)Y;
+      tb.live[p] = (int32_t)out;
+      tb.next_timer[p] = M.ntmin;
+      prog.done[p] = 1;
+      atomicAdd(&st->merged, (unsigned long long)out);
+      if (out > (3 * R) / 4) st->need_grow = 1;
+    }
+  }
+}
+
 // per watermark: the due regions' windows with maxTimestamp <= wm fire (FIRE / FIRE_AND_PURGE and the GC timer
 // coincide with lateness 0); the other entries are copied densely into the region's other buffer.  A workgroup
 // first counts its region's rows (the entries' end / count sector only), reserves them with one atomic on the
@@ -8396,7 +8716,7 @@ int64_t pane_nt_floor(const DevCfg& c, int64_t wm) {
 
 void launch_aggregate(const DevCfg& c0, int64_t wm, const PRec* part, const uint32_t* offs, int32_t T, DevTable tb,
                       AggProg prog, int resume, const AggHot* hot, int64_t n, Status* st, hipStream_t s,
-                      const uint32_t* rsv, int64_t rcap) {
+                      const uint32_t* rsv, int64_t rcap, bool dn) {
   DevCfg c = c0;
   c.nt_floor = pane_nt_floor(c, wm);
   AggHot h{};
@@ -8410,7 +8730,12 @@ void launch_aggregate(const DevCfg& c0, int64_t wm, const PRec* part, const uint
     }
   }
   if (c.dense) {  // the compact table; in a resumed sequence the wide launch takes the regions it left
-    if (!resume && rsv && c.narrow && FW_DT_NDEPTH > 0)  // (its own kernel: the ring's registers)
+    if (!resume && rsv && c.narrow && dn) {  // the narrow-keyed table; what it refuses, the resumed sequence takes
+      // 1024 threads and 4080 slots: 81632 bytes of LDS and 61 VGPRs, so two workgroups share a CU (8 waves a SIMD)
+      // and one region's read-in and write-back run beside the other's record loop (the other shapes)
+      FW_LAUNCH_MAIN((k_dn_aggregate<1024, 4080, 2, 3, 8>), dim3(c.P), dim3(1024), 0, s, c, (const uint64_t*)part, tb,
+                     prog, st, rsv, rcap);
+    } else if (!resume && rsv && c.narrow && FW_DT_NDEPTH > 0)  // (its own kernel: the ring's registers)
       FW_LAUNCH_MAIN((k_dt_aggregate<DT_RECS, true, true>), dim3(c.P), dim3(FW_DT_THREADS), 0, s, c, (const void*)part, offs,
                      T, tb, prog, resume, st, rsv, rcap);
     else

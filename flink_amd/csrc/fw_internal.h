@@ -286,6 +286,7 @@ struct Status {
   int32_t rsv_fallbacks;              // single-pass batches that had to go through classify / scan / scatter
   int32_t acc_refused;                // restore: t-digest rows of a window already present, malformed digests
   int32_t narrow_misses;              // narrow single-pass batches redone because a record had no narrow form
+  int32_t dn_refused;                 // regions the narrow-keyed table (k_dn_aggregate) left to the resumed sequence
 };
 enum {
   FW_STATUS_STATE_LOST = 1,  // a window could not be stored (more in-flight sessions of one key than supported)
@@ -498,10 +499,11 @@ void launch_displaced_any(const DevCfg& c, const int64_t* ts, int64_t n, int32_t
 void launch_scatter_rsv(const DevCfg& c, int64_t wm, const int64_t* key, const int64_t* ts, const int64_t* val,
                         const int32_t* kh, int64_t n, int32_t T, PRec* part, uint32_t* rsv, int64_t rcap, hipStream_t_ s);
 // hot: chunk splitting of long partitions (nullptr = one workgroup per partition); n = records of the push;
-// rsv, rcap: the runs of a single-pass batch (launch_scatter_rsv), nullptr = runs at the scanned offsets offs
+// rsv, rcap: the runs of a single-pass batch (launch_scatter_rsv), nullptr = runs at the scanned offsets offs;
+// dn: a narrow single-pass batch's first launch is the narrow-keyed table's (k_dn_aggregate)
 void launch_aggregate(const DevCfg& c, int64_t wm, const PRec* part, const uint32_t* offs, int32_t T, DevTable tb,
                       AggProg prog, int resume, const AggHot* hot, int64_t n, Status* st, hipStream_t_ s,
-                      const uint32_t* rsv = nullptr, int64_t rcap = 0);
+                      const uint32_t* rsv = nullptr, int64_t rcap = 0, bool dn = false);
 void launch_taint(const DevCfg& c, int64_t wm, const int64_t* key, const int64_t* ts, int64_t n, Status* st,
                   hipStream_t_ s);
 // srow: the ordered-path counts per tile, scanned (T), then raw (T): rows P and P + 1 of the batch's scanned

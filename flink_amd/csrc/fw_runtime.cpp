@@ -89,6 +89,10 @@ struct fw_op {
   int32_t rsv_misses = 0;    // consecutive settles that saw a single-pass batch redone
   int64_t resumptions = 0;   // fw_stats::push_resumptions
   bool rsv_off = false;      // after 3 of them the operator stops trying the single pass
+  int32_t dn_seen = 0;       // Status::dn_refused at the latest settle
+  int32_t dn_misses = 0;     // consecutive pushes of which the narrow-keyed table refused a region
+  bool dn_pending = false;   // such a push is queued and not yet settled
+  bool dn_off = false;       // after 3 of them a narrow batch's first launch is the compact table's again
   int32_t narrow_seen = 0;   // Status::narrow_misses last seen
   bool narrow_off = false;   // a narrow single pass met a record without a narrow form: 16-byte records from then on
   int64_t narrow_batches = 0;  // batches that took the narrow single pass (fw_stats)
@@ -628,6 +632,15 @@ int settle(fw_op* op) {
   } else {
     op->rsv_misses = 0;
   }
+  if (op->dn_pending) {  // the settled sequence held a push whose first aggregate launch was the narrow-keyed table's
+    op->dn_pending = false;
+    if (s.dn_refused != op->dn_seen) {  // regions it refused (long runs of a skewed stream, restored entries): each
+      op->dn_seen = s.dn_refused;       // costs its push a resumption, so after 3 such pushes in a row no more
+      if (++op->dn_misses >= 3) op->dn_off = true;
+    } else {
+      op->dn_misses = 0;
+    }
+  }
   if (op->clear_deferred) {
     // rows the next push's scatter may have added since are side rows; side output never queues
     // early (push_device), so both counts are exactly those of the cleared sequence
@@ -789,6 +802,7 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
   static const bool no_narrow = getenv("FW_NO_NARROW") && atoi(getenv("FW_NO_NARROW"));
   c.narrow = single && !op->narrow_off && c.vtype != FW_VAL_F64 && c.log_s >= 1 && !no_narrow;
   c.ndn0 = c.narrow ? 1 << (c.log_s - 1) : 0;
+  static const bool no_dn = getenv("FW_NO_DN") && atoi(getenv("FW_NO_DN"));  // the compact table leads, as before
   const int32_t T = (int32_t)((n + FW_TILE - 1) / FW_TILE);
   const int64_t m = (int64_t)(c.P + 1) * T;
   // async input: the batch-only kernels run on bstream, after the aggregate that last used this scratch set
@@ -895,11 +909,13 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
     if (cc.td_bhead)  // (sessions: no block has merged blocks yet)
       HIP_OR_RETURN(op, hipMemsetAsync(cc.td_bhead, 0xff, (size_t)cc.pool_blocks * sizeof(int32_t), op->stream));
   }
+  const bool dn = single && cc.dense && cc.narrow && !op->dn_off && !no_dn;  // (launch_aggregate's own condition)
+  op->dn_pending |= dn;
   timed(
       op, K_AGGREGATE,
       [&] {
         fwdev::launch_aggregate(cc, op->wm, S.part, S.hist, S.T, op->tb, op->prog, 0, split ? &op->hot : nullptr,
-                                n, op->d_status, op->stream, single ? S.rsv : nullptr, op->rcap);
+                                n, op->d_status, op->stream, single ? S.rsv : nullptr, op->rcap, dn);
         if (cc.agg == FW_AGG_HLL)
           fwdev::launch_hll_update(cc, S.part, S.hist, S.T, n, op->tb, op->d_status, op->stream);
         if (cc.agg == FW_AGG_ROW)
