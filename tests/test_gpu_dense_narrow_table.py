@@ -196,7 +196,16 @@ def test_gpu_dn_entry_without_narrow_form():
     assert st["push_resumptions"] - before >= 1
 
 
-if __name__ == "__main__":  # the FW_NO_DN child of test_gpu_dn_env_knob_same_rows
-    _op_ = _op(100, max_batch=1 << 17)
-    np.save(sys.argv[1], _drive(_op_, _all_regions_steps()))
-    _op_.close()
+if __name__ == "__main__":  # the FW_NO_DN child: <out> (the all-regions stream), or <out.npz> <dn_util stream> ...
+    if len(sys.argv) > 2:  # (tests/test_gpu_dn_edges.py: every named stream's rows and whole push_resumptions)
+        from tests import dn_util
+        from tests.test_gpu_dn_edges import run_stream
+        res = {}
+        for name in sys.argv[2:]:
+            rows_, _, _, total_ = run_stream(dn_util.stream(name))
+            res[name], res[name + ".resumptions"] = rows_, np.int64(total_)
+        np.savez(sys.argv[1], **res)
+    else:
+        _op_ = _op(100, max_batch=1 << 17)
+        np.save(sys.argv[1], _drive(_op_, _all_regions_steps()))
+        _op_.close()
