@@ -553,6 +553,43 @@ __device__ __forceinline__ void load_records(const DevCfg& c, const int64_t* __r
     }
   }
 }
+// (rec_index for a workgroup of FW_TILE_THREADS: a constant, not a read of the dispatch packet)
+__device__ __forceinline__ int64_t tile_rec_index(int64_t b, int j, int e) {
+  return b + 2 * ((int64_t)j * FW_TILE_THREADS + threadIdx.x) + e;
+}
+// The same lanes and pairs for the pipelined single pass (Long keys, n >= 2), in one straight line: every lane loads
+// 16 bytes per column and pair from an address clamped into the column, so the number of loads in flight does not
+// depend on the path taken and a wait for one piece leaves the later ones in flight.  A pair that starts at the
+// batch's last record is read one record early (8-byte aligned, as every pair of an unaligned column): the reader
+// takes that record from the pair's second place (pair_at; a select here would wait for the load at once).  What
+// lies past `n` is never looked at (the caller skips those records).  COLS: 1 key, 2 ts, 4 val.
+typedef i64x2 i64x2_a8 __attribute__((aligned(8)));
+template <int N>
+__device__ __forceinline__ int64_t pair_at(const int64_t (&a)[N], int j, int64_t i, int64_t n) {
+  return (j & 1) == 0 && i == n - 1 ? a[j + 1] : a[j];
+}
+template <int NP, int COLS>
+__device__ __forceinline__ void load_pairs(const int64_t* __restrict__ key, const int64_t* __restrict__ ts,
+                                           const int64_t* __restrict__ val, int64_t b, int64_t n, int64_t (&k)[2 * NP],
+                                           int64_t (&t)[2 * NP], int64_t (&v)[2 * NP]) {
+#pragma unroll
+  for (int j = 0; j < NP; j++) {
+    const int64_t i = tile_rec_index(b, j, 0);
+    const int64_t ia = min(i, n - 2);
+    if constexpr (COLS & 1) {
+      const i64x2 kk = *reinterpret_cast<const i64x2_a8*>(key + ia);
+      k[2 * j] = kk.x, k[2 * j + 1] = kk.y;
+    }
+    if constexpr (COLS & 2) {
+      const i64x2 tt = *reinterpret_cast<const i64x2_a8*>(ts + ia);
+      t[2 * j] = tt.x, t[2 * j + 1] = tt.y;
+    }
+    if constexpr (COLS & 4) {
+      const i64x2 vv = *reinterpret_cast<const i64x2_a8*>(val + ia);
+      v[2 * j] = vv.x, v[2 * j + 1] = vv.y;
+    }
+  }
+}
 // tile of a classify / scatter workgroup: with FW_XCD_TILES, blocks b, b+8, b+16, ... (one XCD) take
 // consecutive tiles, so the partition runs of neighbouring tiles meet in one L2
 __device__ __forceinline__ int32_t tile_of_block(int32_t T) {
@@ -684,6 +721,31 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* sw, ui
   uint32_t r = sw[wid] + x - v;
   __syncthreads();
   return r;
+}
+
+// the same over FW_TILE_THREADS threads with no serial pass: every wave combines the waves' sums itself (and reads no
+// blockDim: that load would make its wave wait for every global load and store it has in flight).  sw is free again
+// after the caller's next barrier.
+__device__ __forceinline__ uint32_t tile_excl_scan(uint32_t v, uint32_t* sw, uint32_t* total) {
+  constexpr int NWV = FW_TILE_THREADS / 64;
+  const int lane = __lane_id(), wid = threadIdx.x >> 6;
+  uint32_t x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    uint32_t y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) sw[wid] = x;
+  __syncthreads();
+  uint32_t y = lane < NWV ? sw[lane] : 0u;
+#pragma unroll
+  for (int o = 1; o < NWV; o <<= 1) {
+    uint32_t z = __shfl_up(y, o, 64);
+    if (lane >= o) y += z;
+  }
+  *total = __shfl(y, NWV - 1, 64);
+  const uint32_t before = __shfl(y, max(wid - 1, 0), 64);
+  return (wid ? before : 0u) + x - v;
 }
 
 // (gate: a flag the scan runs behind, nullptr = always)
@@ -878,44 +940,32 @@ __global__ __launch_bounds__(FW_TILE_THREADS, FW_SCATTER_WAVES) void k_scatter(D
 // partition's piece is written as one contiguous run (consecutive lanes, consecutive addresses) behind the pieces of
 // the earlier rounds.  Same layout as k_scatter (partition-major runs at the scan offsets, any order inside a run).
 // A batch without compact records goes through k_scatter's body.
-//
-// RSV (dense regions, single pass): no histogram and no scan before it.  Partition p's run is [p * rcap, p * rcap +
-// rsv[p]) and a round reserves its piece of every partition with one global atomic on rsv[p].  A record without a
-// compact form or a run longer than rcap sets rsv[P] (RSV_OVER): then the batch goes through classify, scan and the
-// offset scatter after all (those kernels are gated on rsv[P] and return at once without it).  The error and late
-// counts wait in rsv until the gated classify adds them to the status (RSV_* slots), so a redone batch counts once.
-template <int MODE, int RR, bool RSV, bool NW = false>
+template <int MODE, int RR>
 __device__ __forceinline__ void scatter_staged_body(DevCfg c, int64_t wm, const int64_t* __restrict__ key,
                                                     const int64_t* __restrict__ ts, const int64_t* __restrict__ val,
                                                     const int32_t* __restrict__ kh, int64_t n, int32_t T,
                                                     const uint32_t* __restrict__ offs, PRec* __restrict__ part,
-                                                    DevSide side, Status* st, uint32_t* rsv, int64_t rcap) {
+                                                    DevSide side, Status* st) {
   specialize<MODE>(c);
   extern __shared__ __attribute__((aligned(16))) uint8_t sraw[];
-  // RR: the round's records sorted by partition (NW: narrow 8-byte records)
-  i64x2* stg = reinterpret_cast<i64x2*>(sraw);
-  uint64_t* stg8 = reinterpret_cast<uint64_t*>(sraw);
-  uint16_t* sp = reinterpret_cast<uint16_t*>(sraw + (size_t)RR * (NW ? 8 : 16));  // RR: their partitions
+  i64x2* stg = reinterpret_cast<i64x2*>(sraw);           // RR: the round's records sorted by partition
+  uint16_t* sp = reinterpret_cast<uint16_t*>(sraw + (size_t)RR * 16);  // RR: their partitions
   uint32_t* gb = reinterpret_cast<uint32_t*>(sp + RR);   // P: next free slot of each partition's run
   uint32_t* cs = gb + c.P;                               // P + 1: the round's counts, then their starts in stg
   uint32_t* wsum = cs + c.P + 1;                         // block scan
   const int32_t tile = tile_of_block(T);
-  if constexpr (!RSV) {
-    const bool cmp = c.compact && !*c.wide;  // (uniform: every classify workgroup has finished)
-    if (!cmp) {
-      scatter_direct(c, wm, key, ts, val, kh, n, T, offs, part, side, st, gb, tile);
-      return;
-    }
-    for (int i = threadIdx.x; i < c.P; i += FW_TILE_THREADS) gb[i] = offs[(int64_t)i * T + tile];
+  const bool cmp = c.compact && !*c.wide;  // (uniform: every classify workgroup has finished)
+  if (!cmp) {
+    scatter_direct(c, wm, key, ts, val, kh, n, T, offs, part, side, st, gb, tile);
+    return;
   }
+  for (int i = threadIdx.x; i < c.P; i += FW_TILE_THREADS) gb[i] = offs[(int64_t)i * T + tile];
   const int64_t tbase = (int64_t)tile * FW_TILE;
   const int64_t tend = min(n, tbase + (int64_t)FW_TILE);
   unsigned long long late = 0;
-  int bad_kg = 0, bad_ts = 0, over = 0, nmiss = 0;
   constexpr int RPT = RR / FW_TILE_THREADS;
   const int ppt = (c.P + FW_TILE_THREADS - 1) / FW_TILE_THREADS;
   i64x2* out = reinterpret_cast<i64x2*>(part);
-  uint64_t* out8 = reinterpret_cast<uint64_t*>(part);
   for (int64_t b = tbase; b < tend; b += RR) {
     for (int i = threadIdx.x; i <= c.P; i += FW_TILE_THREADS) cs[i] = 0;
     __syncthreads();
@@ -939,45 +989,25 @@ __device__ __forceinline__ void scatter_staged_body(DevCfg c, int64_t wm, const 
         if (i >= tend) continue;
         const int32_t h = c.key_kind == FW_KEY_HASHED ? hh[j] : key_hash_of(c.key_kind, k[j], kh, i);
         const int32_t p = partition_of(c, k[j], h);
-        if (p < 0) {
-          bad_kg++;
-          continue;
-        }
+        if (p < 0) continue;
         int64_t last = 0;
         int nwin = 0;
         const int cls = classify(c, wm, t[j], &last, &nwin, k[j], 0);
         if (cls == CLS_NORMAL) {
-          const int64_t d = compact_delta(c, last);
-          if (RSV && d < 0) {  // no compact form: the batch takes the offset path
-            over = 1;
-            continue;
-          }
-          if constexpr (NW) {
-            uint64_t nw;
-            if (!narrow_encode(c, k[j], d, vh[j], &nw)) {  // no narrow form: the offset path, with CRecs
-              over = 1;
-              nmiss = 1;
-              continue;
-            }
-            w[jj] = (int64_t)nw;
-          } else {
-            w[jj] = compact_encode(c, k[j], d);
-          }
+          w[jj] = compact_encode(c, k[j], compact_delta(c, last));
           rk[jj] = atomicAdd(&cs[p], 1u);
           pj[jj] = (uint32_t)p;
         } else if (cls == CLS_LATE) {
-          if (!RSV && c.side_output)
+          if (c.side_output)
             side_one(side, st, k[j], t[j], vh[j]);
           else
             late++;
-        } else if (cls == CLS_BADTS) {
-          bad_ts++;
         }
       }
     }
     __syncthreads();
     // exclusive scan of the round's counts (ppt partitions per thread), cs[P] = the round's records
-    constexpr int CQ = ((RSV ? FW_GMAX_P : FW_STAGED_MAX_P) + FW_TILE_THREADS - 1) / FW_TILE_THREADS;
+    constexpr int CQ = (FW_STAGED_MAX_P + FW_TILE_THREADS - 1) / FW_TILE_THREADS;
     uint32_t cq[CQ], sum = 0;
 #pragma unroll
     for (int q = 0; q < CQ; q++) {
@@ -999,51 +1029,21 @@ __device__ __forceinline__ void scatter_staged_body(DevCfg c, int64_t wm, const 
     for (int j = 0; j < RPT; j++) {
       if (pj[j] == 0xffffffffu) continue;
       const uint32_t pos = cs[pj[j]] + rk[j];
-      if constexpr (NW)
-        stg8[pos] = (uint64_t)w[j];
-      else
-        stg[pos] = i64x2{w[j], v[j]};
+      stg[pos] = i64x2{w[j], v[j]};
       sp[pos] = (uint16_t)pj[j];
-    }
-    if constexpr (RSV) {  // this round's piece of every partition it has records for
-      for (int i = threadIdx.x; i < c.P; i += FW_TILE_THREADS) {
-        const uint32_t m = cs[i + 1] - cs[i];
-        if (m == 0) continue;
-        const uint32_t g = atomicAdd(&rsv[i], m);
-        if ((int64_t)g + m > rcap) {
-          over = 1;
-          gb[i] = 0xffffffffu;
-        } else {
-          gb[i] = (uint32_t)((int64_t)i * rcap + g);
-        }
-      }
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < total; i += FW_TILE_THREADS) {
       const uint32_t pp = sp[i];
-      if (RSV && gb[pp] == 0xffffffffu) continue;
-      if constexpr (NW)
-        out8[gb[pp] + (i - cs[pp])] = stg8[i];
-      else
-        out[gb[pp] + (i - cs[pp])] = stg[i];
+      out[gb[pp] + (i - cs[pp])] = stg[i];
     }
     __syncthreads();
-    if constexpr (!RSV) {
-      for (int i = threadIdx.x; i < c.P; i += FW_TILE_THREADS) gb[i] += cs[i + 1] - cs[i];
-      __syncthreads();
-    }
+    for (int i = threadIdx.x; i < c.P; i += FW_TILE_THREADS) gb[i] += cs[i + 1] - cs[i];
+    __syncthreads();
   }
-  if constexpr (RSV) {
-    if (over) rsv[c.P + RSV_OVER] = 1;
-    if (NW && nmiss) rsv[c.P + FW_RSV_NARROW] = 1;
-    if (bad_kg) atomicAdd(&rsv[c.P + RSV_KG], (uint32_t)bad_kg);
-    if (bad_ts) atomicAdd(&rsv[c.P + RSV_TS], (uint32_t)bad_ts);
-    if (late) atomicAdd(reinterpret_cast<unsigned long long*>(rsv + c.P + RSV_LATE), late);
-  } else if (late) {
-    atomicAdd(&st->late_dropped, late);
-  }
+  if (late) atomicAdd(&st->late_dropped, late);
 }
-// the offset form (gate: the single pass's RSV_OVER word, the batch comes here only when it is set; nullptr = always)
+// (gate: the single pass's RSV_OVER word, the batch comes here only when it is set; nullptr = always)
 template <int MODE, int RR>
 __global__ __launch_bounds__(FW_TILE_THREADS) void k_scatter_staged(DevCfg c, int64_t wm, const int64_t* __restrict__ key,
                                                                    const int64_t* __restrict__ ts,
@@ -1053,16 +1053,215 @@ __global__ __launch_bounds__(FW_TILE_THREADS) void k_scatter_staged(DevCfg c, in
                                                                    PRec* __restrict__ part, DevSide side, Status* st,
                                                                    const uint32_t* __restrict__ gate) {
   if (gate && !gate[0]) return;  // (the batch went through the single pass)
-  scatter_staged_body<MODE, RR, false>(c, wm, key, ts, val, kh, n, T, offs, part, side, st, nullptr, 0);
+  scatter_staged_body<MODE, RR>(c, wm, key, ts, val, kh, n, T, offs, part, side, st);
 }
-// the single pass (tumbling windows, dense regions); NW: narrow records, rcap in 8-byte records
+
+// ---- K2, the single pass (tumbling windows, dense regions): no histogram and no scan before it.  Partition p's run
+// is [p * rcap, p * rcap + rsv[p]) and a round of RR records reserves its piece of every partition with one global
+// atomic on rsv[p].  A record without a compact form or a run longer than rcap sets rsv[P] (RSV_OVER): then the batch
+// goes through classify, scan and the offset scatter after all (those kernels are gated on rsv[P] and return at once
+// without it).  The error and late counts wait in rsv until the gated classify adds them to the status (RSV_* slots),
+// so a redone batch counts once.  NW: narrow 8-byte records, rcap in 8-byte records.
+struct RsvCounts {
+  unsigned long long late = 0;
+  int bad_kg = 0, bad_ts = 0, over = 0, nmiss = 0;
+};
+// one record: its partition and its word *w, or -1 and the reason counted
+template <bool NW>
+__device__ __forceinline__ int32_t rsv_record(const DevCfg& c, int64_t wm, int64_t k, int64_t t, int64_t v,
+                                              const int32_t* __restrict__ kh, int64_t i, int64_t* w, RsvCounts& n) {
+  const int32_t p = partition_of(c, k, key_hash_of(c.key_kind, k, kh, i));
+  if (p < 0) {
+    n.bad_kg++;
+    return -1;
+  }
+  int64_t last = 0;
+  int nwin = 0;
+  const int cls = classify(c, wm, t, &last, &nwin, k, 0);
+  if (cls == CLS_NORMAL) {
+    const int64_t d = compact_delta(c, last);
+    if (d < 0) {  // no compact form: the batch takes the offset path
+      n.over = 1;
+      return -1;
+    }
+    if constexpr (NW) {
+      uint64_t nw;
+      if (!narrow_encode(c, k, d, v, &nw)) {  // no narrow form: the offset path, with CRecs
+        n.over = 1;
+        n.nmiss = 1;
+        return -1;
+      }
+      *w = (int64_t)nw;
+    } else {
+      *w = compact_encode(c, k, d);
+    }
+    return p;
+  }
+  if (cls == CLS_LATE)
+    n.late++;
+  else if (cls == CLS_BADTS)
+    n.bad_ts++;
+  return -1;
+}
+template <bool NW>
+__device__ __forceinline__ void rsv_counts_out(const DevCfg& c, uint32_t* rsv, const RsvCounts& n) {
+  if (n.over) rsv[c.P + RSV_OVER] = 1;
+  if (NW && n.nmiss) rsv[c.P + FW_RSV_NARROW] = 1;
+  if (n.bad_kg) atomicAdd(&rsv[c.P + RSV_KG], (uint32_t)n.bad_kg);
+  if (n.bad_ts) atomicAdd(&rsv[c.P + RSV_TS], (uint32_t)n.bad_ts);
+  if (n.late) atomicAdd(reinterpret_cast<unsigned long long*>(rsv + c.P + RSV_LATE), n.late);
+}
+// Persistent and pipelined across rounds: the grid is one workgroup per CU (launch_scatter_rsv), each takes rounds
+// blockIdx.x, blockIdx.x + gridDim.x, ... of the batch (a round never straddles a tile: FW_TILE is a multiple of RR;
+// FW_XCD_TILES does not apply).  One iteration ranks round r in two halves out of the registers its loads went to an
+// iteration ago, and puts each half of round r + 1 in flight in the same registers as soon as they are free; then it
+// copies the staged round r - 1 out, issues round r's reservations, and scans and stages round r in LDS.  The loads,
+// the copy-out's stores and the reservations' round trips run under the ranking, the scan and the staging of other
+// halves and rounds, never under a barrier of their own.  cs / cp: the counts of the round being ranked, the starts
+// of the staged one (they swap).
 template <int RR, bool NW>
 __global__ __launch_bounds__(FW_TILE_THREADS) void k_scatter_rsv(DevCfg c, int64_t wm, const int64_t* __restrict__ key,
                                                                 const int64_t* __restrict__ ts,
                                                                 const int64_t* __restrict__ val,
-                                                                const int32_t* __restrict__ kh, int64_t n, int32_t T,
+                                                                const int32_t* __restrict__ kh, int64_t n,
                                                                 PRec* __restrict__ part, uint32_t* rsv, int64_t rcap) {
-  scatter_staged_body<M_TUMB, RR, true, NW>(c, wm, key, ts, val, kh, n, T, nullptr, part, DevSide{}, nullptr, rsv, rcap);
+  static_assert(FW_TILE % RR == 0 && RR % (4 * FW_TILE_THREADS) == 0 && RR <= 65536 && FW_GMAX_P < 65535);
+  specialize<M_TUMB>(c);
+  i64x2* out = reinterpret_cast<i64x2*>(part);
+  uint64_t* out8 = reinterpret_cast<uint64_t*>(part);
+  RsvCounts cnt;
+  if (n < 2) {  // no pair to load: the one record goes straight to its run
+    if (n == 1 && blockIdx.x == 0 && threadIdx.x == 0) {
+      int64_t w = 0;
+      const int64_t v0 = val[0];
+      const int32_t p = rsv_record<NW>(c, wm, key[0], ts[0], v0, kh, 0, &w, cnt);
+      if (p >= 0) {
+        const uint32_t g = atomicAdd(&rsv[p], 1u);
+        if ((int64_t)g + 1 > rcap)
+          cnt.over = 1;
+        else if constexpr (NW)
+          out8[(int64_t)p * rcap + g] = (uint64_t)w;
+        else
+          out[(int64_t)p * rcap + g] = i64x2{w, v0};
+      }
+      rsv_counts_out<NW>(c, rsv, cnt);
+    }
+    return;
+  }
+  extern __shared__ __attribute__((aligned(16))) uint8_t sraw[];
+  i64x2* stg = reinterpret_cast<i64x2*>(sraw);  // RR: the staged round's records sorted by partition
+  uint64_t* stg8 = reinterpret_cast<uint64_t*>(sraw);
+  uint16_t* sp = reinterpret_cast<uint16_t*>(sraw + (size_t)RR * (NW ? 8 : 16));  // RR: their partitions
+  uint32_t* gb = reinterpret_cast<uint32_t*>(sp + RR);  // P: where the staged round's piece of each run goes
+  uint32_t* cs = gb + c.P;                              // P: the ranked round's counts, then their starts in stg
+  uint32_t* cp = cs + c.P;                              // P: the staged round's starts
+  uint32_t* wsum = gb + 3 * c.P;                        // block scan
+  constexpr int RPT = RR / FW_TILE_THREADS;
+  constexpr int H = RPT / 2;               // a round is loaded and ranked in two halves
+  constexpr int PPT = RR == 8192 ? 1 : 2;  // partitions per thread (launch_scatter_rsv: RR 8192 up to 1024 partitions)
+  int64_t r = blockIdx.x;
+  int64_t b = min(r * RR, n), end = min(n, b + RR);
+  int64_t k[2][H], t[2][H], v[2][H];
+#pragma unroll
+  for (int hf = 0; hf < 2; hf++) load_pairs<H / 2, NW ? 7 : 3>(key, ts, val, b + hf * (RR / 2), n, k[hf], t[hf], v[hf]);
+  for (int i = threadIdx.x; i < c.P; i += FW_TILE_THREADS) cs[i] = 0;
+  uint32_t staged = 0;             // records of the staged round
+  uint32_t gm[PPT] = {}, gg[PPT];  // the staged round's reservations: the pieces' lengths, the runs' lengths before
+  __syncthreads();
+  for (;;) {
+    // this round: each half classified and ranked in its partitions, then the same half of the next round's loads
+    // into the registers it has left (past the last round they fetch the batch's end again and nobody looks).  So
+    // the second half's loads, the last copy-out's stores and the reservations are in flight under the first half's
+    // arithmetic, and the next round's first half under the second's.  A narrow record has taken its value in; a
+    // 16-byte one needs it only when it is staged, so this round's values are loaded here too.
+    const bool more = b < n;
+    const int64_t bn = min((r += gridDim.x) * RR, n), endn = min(n, bn + RR);
+    uint32_t pr[RPT];  // partition << 16 | rank in the round's piece of it (RR <= 2^16), ~0: no record to stage
+    int64_t w[RPT];
+#pragma unroll
+    for (int hf = 0; hf < 2; hf++) {
+#pragma unroll
+      for (int jh = 0; jh < H; jh++) {
+        const int j = hf * H + jh;
+        const int64_t i = tile_rec_index(b + hf * (RR / 2), jh >> 1, jh & 1);
+        pr[j] = 0xffffffffu;
+        if (i >= end) continue;
+        const int32_t p = rsv_record<NW>(c, wm, pair_at(k[hf], jh, i, n), pair_at(t[hf], jh, i, n),
+                                         NW ? pair_at(v[hf], jh, i, n) : 0, kh, i, &w[j], cnt);
+        if (p >= 0) pr[j] = (uint32_t)p << 16 | atomicAdd(&cs[p], 1u);
+      }
+      if constexpr (NW) load_pairs<H / 2, 7>(key, ts, val, bn + hf * (RR / 2), n, k[hf], t[hf], v[hf]);
+    }
+    if constexpr (!NW) {  // (16-byte records: both halves behind the ranking, or the registers run out)
+#pragma unroll
+      for (int hf = 0; hf < 2; hf++) {
+        load_pairs<H / 2, 3>(key, ts, val, bn + hf * (RR / 2), n, k[hf], t[hf], v[hf]);
+        load_pairs<H / 2, 4>(key, ts, val, b + hf * (RR / 2), n, k[hf], t[hf], v[hf]);
+      }
+    }
+    // the staged round's reservations are back: where its pieces go
+#pragma unroll
+    for (int q = 0; q < PPT; q++) {
+      const int i = threadIdx.x + q * FW_TILE_THREADS;
+      if (gm[q] == 0) continue;
+      if ((int64_t)gg[q] + gm[q] > rcap) {
+        cnt.over = 1;
+        gb[i] = 0xffffffffu;
+      } else {
+        gb[i] = (uint32_t)((int64_t)i * rcap + gg[q]);
+      }
+    }
+    __syncthreads();
+    // the staged round's pieces go out, each one contiguous run
+    for (uint32_t i = threadIdx.x; i < staged; i += FW_TILE_THREADS) {
+      const uint32_t pp = sp[i];
+      if (gb[pp] == 0xffffffffu) continue;
+      if constexpr (NW)
+        out8[gb[pp] + (i - cp[pp])] = stg8[i];
+      else
+        out[gb[pp] + (i - cp[pp])] = stg[i];
+    }
+    if (!more) break;  // (uniform; this iteration's round was the empty one past the workgroup's last)
+    // this round's piece of every partition it has records for (relaxed, device scope: the kernel's end orders them
+    // against the aggregate); the answers are read behind the next round's ranking
+#pragma unroll
+    for (int q = 0; q < PPT; q++) {
+      const int i = threadIdx.x + q * FW_TILE_THREADS;
+      gm[q] = i < c.P ? cs[i] : 0u;
+      if (gm[q]) gg[q] = atomicAdd(&rsv[i], gm[q]);
+    }
+    // exclusive scan of the round's counts (its barrier also ends the copy-out's reads of stg, sp and cp)
+    uint32_t cq[PPT], sum = 0;
+#pragma unroll
+    for (int q = 0; q < PPT; q++) {
+      const int pp = threadIdx.x * PPT + q;
+      cq[q] = pp < c.P ? cs[pp] : 0u;
+      sum += cq[q];
+    }
+    uint32_t e = tile_excl_scan(sum, wsum, &staged);
+#pragma unroll
+    for (int q = 0; q < PPT; q++) {
+      const int pp = threadIdx.x * PPT + q;
+      if (pp < c.P) cs[pp] = e;
+      e += cq[q];
+    }
+    for (int i = threadIdx.x; i < c.P; i += FW_TILE_THREADS) cp[i] = 0;  // the next round's counts
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < RPT; j++) {
+      if (pr[j] == 0xffffffffu) continue;
+      const uint32_t pos = cs[pr[j] >> 16] + (pr[j] & 0xffffu);
+      if constexpr (NW)
+        stg8[pos] = (uint64_t)w[j];
+      else
+        stg[pos] = i64x2{w[j], pair_at(v[j / H], j % H, tile_rec_index(b + (j / H) * (RR / 2), (j % H) >> 1, 0), n)};
+      sp[pos] = (uint16_t)(pr[j] >> 16);
+    }
+    b = bn, end = endn;
+    uint32_t* const x = cs;  // (the next iteration's first barrier orders the staging before the copy-out)
+    cs = cp, cp = x;
+  }
+  rsv_counts_out<NW>(c, rsv, cnt);
 }
 
 // ---- K2b: ordered compaction of the ordered-path records of a tile (skipped by tiles that have none).
@@ -8680,8 +8879,8 @@ void launch_scatter_rsv(const DevCfg& c, int64_t wm, const int64_t* key, const i
                         const int32_t* kh, int64_t n, int32_t T, PRec* part, uint32_t* rsv, int64_t rcap, hipStream_t s) {
   const bool big = c.P <= 1024;
   const int rr = big ? 8192 : 4096;
-  const size_t sl = (size_t)rr * ((c.narrow ? 8 : sizeof(i64x2)) + sizeof(uint16_t)) +
-                    (2 * (size_t)c.P + 1) * sizeof(uint32_t) + (FW_TILE_THREADS / 64 + 1) * sizeof(uint32_t);
+  const size_t sl = (size_t)rr * ((c.narrow ? 8 : sizeof(i64x2)) + sizeof(uint16_t)) + 3 * (size_t)c.P * sizeof(uint32_t) +
+                    (FW_TILE_THREADS / 64) * sizeof(uint32_t);
   static bool attr = false;
   if (!attr) {  // LDS beyond 64 KB
     for (const void* f : {(const void*)k_scatter_rsv<8192, false>, (const void*)k_scatter_rsv<4096, false>,
@@ -8689,19 +8888,30 @@ void launch_scatter_rsv(const DevCfg& c, int64_t wm, const int64_t* key, const i
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
+  // persistent: one workgroup per CU (its LDS admits no second), each walks the batch's rounds at that stride
+  static thread_local int cu_dev = -1, cus = 0;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev != cu_dev) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    cu_dev = dev;
+  }
+  const int64_t rounds = (n + rr - 1) / rr;
+  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(rounds, cus)));
+  (void)T;
   // (narrow: a partition's run holds twice as many 8-byte records in the same bytes)
   if (c.narrow && big)
-    FW_LAUNCH_MAIN((k_scatter_rsv<8192, true>), dim3(T), dim3(FW_TILE_THREADS), sl, s, c, wm, key, ts, val, kh, n, T,
-                   part, rsv, 2 * rcap);
+    FW_LAUNCH_MAIN((k_scatter_rsv<8192, true>), grid, dim3(FW_TILE_THREADS), sl, s, c, wm, key, ts, val, kh, n, part, rsv,
+                   2 * rcap);
   else if (c.narrow)
-    FW_LAUNCH_MAIN((k_scatter_rsv<4096, true>), dim3(T), dim3(FW_TILE_THREADS), sl, s, c, wm, key, ts, val, kh, n, T,
-                   part, rsv, 2 * rcap);
+    FW_LAUNCH_MAIN((k_scatter_rsv<4096, true>), grid, dim3(FW_TILE_THREADS), sl, s, c, wm, key, ts, val, kh, n, part, rsv,
+                   2 * rcap);
   else if (big)
-    FW_LAUNCH_MAIN((k_scatter_rsv<8192, false>), dim3(T), dim3(FW_TILE_THREADS), sl, s, c, wm, key, ts, val, kh, n, T,
-                   part, rsv, rcap);
+    FW_LAUNCH_MAIN((k_scatter_rsv<8192, false>), grid, dim3(FW_TILE_THREADS), sl, s, c, wm, key, ts, val, kh, n, part, rsv,
+                   rcap);
   else
-    FW_LAUNCH_MAIN((k_scatter_rsv<4096, false>), dim3(T), dim3(FW_TILE_THREADS), sl, s, c, wm, key, ts, val, kh, n, T,
-                   part, rsv, rcap);
+    FW_LAUNCH_MAIN((k_scatter_rsv<4096, false>), grid, dim3(FW_TILE_THREADS), sl, s, c, wm, key, ts, val, kh, n, part, rsv,
+                   rcap);
 }
 
 // panes: maxTimestamp of the earliest window ending after wm (windows [s, s + size), s = offset mod slide)

@@ -87,7 +87,7 @@
 #ifndef FW_DT_NDEPTH
 #define FW_DT_NDEPTH 2  // narrow records: rounds of raw pairs in flight (0: two widened rounds, as 16-byte records)
 #endif
-// LDS-staged scatters (scatter_staged_body): the partitions' counters and run bases sit in LDS beside the staged
+// LDS-staged scatters (scatter_staged_body, k_scatter_rsv): the partitions' counters and run bases sit in LDS beside the staged
 // records, which bounds P
 #define FW_GMAX_P 2048        // single-pass reservation scatter (k_scatter_rsv, rsv_eligible) and its gated fallback
 #define FW_STAGED_MAX_P 4096  // LDS-staged offset scatter (k_scatter_staged): up to this many partitions
@@ -485,7 +485,7 @@ void launch_scatter(const DevCfg& c, int64_t wm, const int64_t* key, const int64
                     const int32_t* kh, int64_t n, int32_t T, uint32_t* offs, PRec* part, int64_t* sk,
                     int64_t* stt, int64_t* sv, int32_t* skh, DevSide side, Status* st, hipStream_t_ s,
                     const uint32_t* gate = nullptr);
-// single-pass scatter of a dense compact batch (k_scatter_staged<..., true>): partition p's run at [p * rcap,
+// single-pass scatter of a dense compact batch (k_scatter_rsv, persistent: one workgroup per CU): partition p's run at [p * rcap,
 // p * rcap + rsv[p]); rsv holds P + FW_RSV_WORDS words, zeroed before the launch.  When rsv[P] is set after it, the
 // batch goes through launch_classify_hist / launch_scan / launch_scatter gated on rsv (they do nothing otherwise).
 #define FW_RSV_WORDS 8
