@@ -17,6 +17,7 @@ FW_ERR_CAPACITY = -5
 FW_ERR_UNSUPPORTED = -6
 FW_ERR_STATE = -7
 FW_ERR_DISPLACED = -8
+FW_ERR_TIME_RANGE = -9
 
 FW_TUMBLING, FW_SLIDING, FW_SESSION, FW_COUNT = 0, 1, 2, 3
 FW_VAL_I64, FW_VAL_I32, FW_VAL_F64, FW_VAL_I16, FW_VAL_I8, FW_VAL_F32 = 0, 1, 2, 3, 4, 5

@@ -147,8 +147,17 @@ __device__ __forceinline__ int64_t f64_unsortable(int64_t s) { return s >= 0 ? s
 __device__ __forceinline__ bool displaced(const DevCfg& c, int64_t ts) {
   return jrem(jadd(jsub(ts, c.offset), c.slide), c.slide, c.mag_slide, c.l_slide) < 0;
 }
+// A tumbling record that lies at or above its window's end: the end wrapped past Long.MAX_VALUE, or
+// ts - offset + size did and the start wrapped to the bottom of the range.  The operator is exact on it; a pre-shuffle
+// combiner is not (the receiver takes a partial's window start for the records' timestamps when it counts late
+// records), so the extraction refuses once one was taken (FW_STATUS_ABOVE_WINDOW).
+__device__ __forceinline__ bool above_window(const DevCfg& c, int64_t ts, int64_t last) {
+  return c.assigner == FW_TUMBLING && jadd(last, c.size) <= ts;
+}
 // ------------------------------------------------------------------ record classes
-enum { CLS_NORMAL = 0, CLS_SLOW = 1, CLS_LATE = 2, CLS_SKIP = 3, CLS_BADTS = 4 };
+// CLS_RANGE: a timestamp at an end of the long range that this operator refuses (FW_ERR_TIME_RANGE, DESIGN.md
+// "Event-time arithmetic"); the host refuses host columns before anything is queued, device columns arrive here
+enum { CLS_NORMAL = 0, CLS_SLOW = 1, CLS_LATE = 2, CLS_SKIP = 3, CLS_BADTS = 4, CLS_RANGE = 5 };
 
 // Windows of a record, newest first (SlidingEventTimeWindows.java:71-75 loop order).
 __device__ __forceinline__ int num_windows(const DevCfg& c, int64_t ts, int64_t* last_start) {
@@ -176,8 +185,24 @@ __device__ __forceinline__ bool taint_has(const DevCfg& c, int64_t key) {
   return false;
 }
 // a session element that may fire, merge into a fired window or be dropped: it needs arrival order
+// (so does one whose window [ts, ts + gap) wraps past Long.MAX_VALUE: TimeWindow.intersects does not hold between it
+// and its neighbours by start, which the parallel path's merge of sorted windows would join)
 __device__ __forceinline__ bool session_ordered(const DevCfg& c, int64_t wm, int64_t ts) {
-  return ts == LMIN || jsub(jadd(ts, c.gap), 1) <= wm;
+  const int64_t e = jadd(ts, c.gap);
+  return ts == LMIN || e < ts || jsub(e, 1) <= wm;
+}
+// the bottom of the long range: ts - size - 2 slide leaves it (ts - offset + slide and the walk down from the newest
+// start then wrap; a sliding record there has no window, or its walk does not end: the runaway set)
+__device__ __forceinline__ bool bottom_range(const DevCfg& c, int64_t ts) {
+  const int64_t a = jsub(ts, c.size), b = jsub(a, c.slide), d = jsub(b, c.slide);
+  return a > ts || b > a || d > b;
+}
+// sliding windows kept as panes refuse ts (last: its newest window's start): that window's end wraps, or
+// ts - offset + slide does (the start then lands above ts and may itself wrap to the bottom), or ts is in the bottom
+// range
+__device__ __forceinline__ bool pane_range(const DevCfg& c, int64_t ts, int64_t last) {
+  const int64_t u = jsub(ts, c.offset);
+  return jadd(last, c.size) < last || jadd(u, c.slide) < u || bottom_range(c, ts);
 }
 
 // class of a record against watermark wm; for CLS_NORMAL also its windows (newest start, count).
@@ -210,6 +235,9 @@ __device__ __forceinline__ int classify(const DevCfg& c, int64_t wm, int64_t ts,
       *last_out = last;
       *k_out = 1;
     }
+    // k_fire_panes takes window ends in the order of their panes' starts: a record whose newest window's end wraps
+    // past Long.MAX_VALUE, or that lies in the bottom range, is refused under any watermark
+    if (pane_range(c, ts, last)) return CLS_RANGE;
     if (cleanup_of(jadd(last, c.size), 0) > wm) return CLS_NORMAL;
     return ts <= wm ? CLS_LATE : CLS_SKIP;
   }
@@ -222,6 +250,17 @@ __device__ __forceinline__ int classify(const DevCfg& c, int64_t wm, int64_t ts,
   if (k == 0) return jadd(ts, c.lateness) <= wm ? CLS_LATE : CLS_SKIP;
   const int64_t newest_end = jadd(last, c.size);
   const int64_t oldest_end = jadd(jsub(last, (int64_t)(k - 1) * c.slide), c.size);
+  if (k > 1) {
+    // The two tests below take the oldest window's end for the smallest and the newest one's for the largest, which
+    // holds while no end wraps past Long.MAX_VALUE.  The newest end is the first to wrap (the starts walk down
+    // without wrapping: s > ts - size); then the ordered replay decides window by window (one window: the tests are
+    // that window's own).  The t-digest takes a record's windows that are not late as the newest ones (the prefix
+    // below, td_ovn on the ordered path), which a wrapped newest end breaks: refused.
+    if (newest_end < last) return c.agg == FW_AGG_TDIGEST ? CLS_RANGE : CLS_SLOW;
+    // the runaway set: the walk has not ended after wpr windows, it wrapped below Long.MIN_VALUE (the reference's
+    // own loop then runs for about 2^64 / slide steps)
+    if (k == c.wpr && jsub(last, (int64_t)k * c.slide) > jsub(ts, c.size)) return CLS_RANGE;
+  }
   if (jsub(oldest_end, 1) > wm) return CLS_NORMAL;  // every window: maxTimestamp > wm
   if (cleanup_of(newest_end, c.lateness) <= wm)     // every window late (isWindowLate)
     return jadd(ts, c.lateness) <= wm ? CLS_LATE : CLS_SKIP;  // isElementLate
@@ -656,7 +695,7 @@ __global__ __launch_bounds__(FW_TILE_THREADS) void k_classify_hist(DevCfg c, int
   const int32_t tile = blockIdx.x;
   const int64_t base = (int64_t)tile * FW_TILE;
   const int64_t end = min(n, base + (int64_t)FW_TILE);
-  int bad_kg = 0, bad_ts = 0, wide = 0;
+  int bad_kg = 0, bad_ts = 0, bad_range = 0, wide = 0, above = 0;
   unsigned slow = 0;
   const int taint = c.assigner == FW_SESSION ? st->taint_any : 0;
   for (int64_t b = base; b < end; b += (int64_t)blockDim.x * FW_RPT) {
@@ -678,10 +717,13 @@ __global__ __launch_bounds__(FW_TILE_THREADS) void k_classify_hist(DevCfg c, int
       if (cls == CLS_NORMAL) {
         atomicAdd(&lh[p], 1u);
         if (c.compact && compact_delta(c, last) < 0) wide = 1;
+        if (above_window(c, t[j], last)) above = 1;
       } else if (cls == CLS_SLOW)
         slow++;
       else if (cls == CLS_BADTS)
         bad_ts++;
+      else if (cls == CLS_RANGE)
+        bad_range++;
     }
   }
   if (slow) atomicAdd(&lh[c.P], slow);
@@ -690,6 +732,8 @@ __global__ __launch_bounds__(FW_TILE_THREADS) void k_classify_hist(DevCfg c, int
   if (threadIdx.x == 0) hist[(int64_t)(c.P + 1) * T + tile] = lh[c.P];
   if (bad_kg) atomicAdd(&st->kg_errors, bad_kg);
   if (bad_ts) atomicAdd(&st->ts_errors, bad_ts);
+  if (bad_range) atomicAdd(&st->range_errors, bad_range);
+  if (above) atomicOr(&st->flags, FW_STATUS_ABOVE_WINDOW);
   if (wide) atomicOr(c.wide, 1);
 }
 
@@ -1080,7 +1124,7 @@ __device__ __forceinline__ int32_t rsv_record(const DevCfg& c, int64_t wm, int64
   const int cls = classify(c, wm, t, &last, &nwin, k, 0);
   if (cls == CLS_NORMAL) {
     const int64_t d = compact_delta(c, last);
-    if (d < 0) {  // no compact form: the batch takes the offset path
+    if (d < 0 || above_window(c, t, last)) {  // no compact form (or the classify pass has to note it): the offset path
       n.over = 1;
       return -1;
     }
@@ -3124,7 +3168,9 @@ __device__ void replay_session(const SlowCtx& x, int32_t p, int64_t k, int64_t t
     if (stt != want) continue;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     const Entry& e = r.ent[s];
-    if (e.key != k || !(ws <= e.end && we >= e.start)) continue;  // TimeWindow.intersects
+    // TimeWindow.intersects -- or the same window: a wrapped window (we < ws) does not intersect its equal, but
+    // MergingWindowSet's mapping is keyed by the window, so the two share one state
+    if (e.key != k || !((ws <= e.end && we >= e.start) || (ws == e.start && we == e.end))) continue;
     if (first < 0) first = (int32_t)s;
     n_in++;
     cs = min(cs, e.start);
@@ -8790,7 +8836,8 @@ __global__ __launch_bounds__(256) void k_displaced_any(DevCfg c, const int64_t* 
   bool any = false;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t t = ts[i];
-    any |= t != LMIN && displaced(c, t);
+    // (a record the pane operator refuses for its place in the long range is classify's, under any watermark)
+    any |= t != LMIN && displaced(c, t) && !pane_range(c, t, wstart(t, c.offset, c.slide, c.mag_slide, c.l_slide));
   }
   if (__any(any) && __lane_id() == 0) atomicOr(flag, 1);
 }

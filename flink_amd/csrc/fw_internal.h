@@ -287,6 +287,7 @@ struct Status {
   int32_t acc_refused;                // restore: t-digest rows of a window already present, malformed digests
   int32_t narrow_misses;              // narrow single-pass batches redone because a record had no narrow form
   int32_t dn_refused;                 // regions the narrow-keyed table (k_dn_aggregate) left to the resumed sequence
+  int32_t range_errors;               // records of device columns refused for their timestamp (FW_ERR_TIME_RANGE)
 };
 enum {
   FW_STATUS_STATE_LOST = 1,  // a window could not be stored (more in-flight sessions of one key than supported)
@@ -294,7 +295,8 @@ enum {
   FW_STATUS_MERGE_LATE = 4,
   FW_STATUS_SIDE_FULL = 8,
   FW_STATUS_POOL = 16,       // the accumulator block pool (HyperLogLog registers, t-digests) ran out of blocks
-  FW_STATUS_TD_UNION = 32    // a late session firing joined more centroids than its union scratch holds
+  FW_STATUS_TD_UNION = 32,   // a late session firing joined more centroids than its union scratch holds
+  FW_STATUS_ABOVE_WINDOW = 64  // a tumbling record at or above its window's end was taken (no error: fw_combine_extract refuses)
 };
 // a region takes new windows only up to this load; beyond it the kernel suspends and the table grows
 __host__ __device__ inline int32_t region_limit(int32_t log_r) { return (int32_t)((3ll << log_r) >> 2); }

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/flink_window.h"
+#include "fw_range.h"
 
 namespace {
 
@@ -50,7 +51,10 @@ constexpr int64_t LMIN = INT64_MIN;
 // GF_FPEND: ContinuousEventTimeTrigger's timer at the window's fire time is registered
 enum : uint32_t { GF_TIMER = 1u, GF_TOUCH = 2u, GF_FIRE = 4u, GF_CLEAN = 8u, GF_FPEND = 16u };
 constexpr unsigned long long CF_MAX_FIRINGS = 1ull << 20;  // of one window in one watermark advance
-enum : uint32_t { LF_NO_TS = 1u, LF_KEY_GROUP = 2u, LF_MAP_FULL = 4u, LF_ELEMS = 8u, LF_MERGE_LATE = 16u, LF_MERGE_WIDE = 32u };
+enum : uint32_t {
+  LF_NO_TS = 1u, LF_KEY_GROUP = 2u, LF_MAP_FULL = 4u, LF_ELEMS = 8u, LF_MERGE_LATE = 16u, LF_MERGE_WIDE = 32u,
+  LF_RANGE = 64u  // a sliding timestamp of the runaway set (FW_ERR_TIME_RANGE)
+};
 constexpr uint32_t G_EMPTY = 0u, G_BUSY = 1u, G_LIVE = 2u, G_TOMB = 3u;
 
 struct LCfg {
@@ -58,6 +62,7 @@ struct LCfg {
   int64_t size, slide, offset, lateness, trig_n, ev_n;
   double thr;
   int64_t trig_i;  // ContinuousEventTimeTrigger's interval
+  int64_t wcap;    // sliding: the most windows of a record, ceil(size / slide) + 1 (a displaced record's extra one)
 };
 
 struct LCounters {
@@ -130,9 +135,15 @@ __device__ __forceinline__ void for_windows(const LCfg& c, int64_t ts, int64_t w
     if (!(w_cleanup(c, s) <= wm)) f(s);
     return;
   }
+  // (at most wcap windows: the walk of a runaway timestamp, refused before it gets here, would not end)
   const int64_t last = w_start_of(ts, c.offset, c.slide);  // SlidingEventTimeWindows.java:67-81
-  for (int64_t s = last; s > jsub(ts, c.size); s = jsub(s, c.slide))
+  int64_t k = 0;
+  for (int64_t s = last; s > jsub(ts, c.size) && k < c.wcap; s = jsub(s, c.slide), k++)
     if (!(w_cleanup(c, s) <= wm)) f(s);
+}
+// the runaway set of the sliding assigner (fw_range.h fw_sliding_runaway; DESIGN.md "Event-time arithmetic")
+__host__ __device__ __forceinline__ bool runaway(const LCfg& c, int64_t ts) {
+  return c.assigner == FW_SLIDING && fw_sliding_runaway(c.size, c.slide, c.offset, c.wcap, ts);
 }
 
 // ---------------------------------------------------------------- group map
@@ -230,6 +241,10 @@ __global__ __launch_bounds__(256) void k_lp_count(LCfg c, LState S, const int64_
     const int32_t kg = key_group(key_hash_of(c.key_kind, key[i], kh, i), c.max_par);
     if ((uint32_t)(kg - c.kg0) >= (uint32_t)c.nkg) {
       atomicOr(&S.ctr->flags, LF_KEY_GROUP);
+      continue;
+    }
+    if (runaway(c, t)) {
+      atomicOr(&S.ctr->flags, LF_RANGE);
       continue;
     }
     uint32_t k = 0;
@@ -1315,7 +1330,9 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
         __atomic_signal_fence(__ATOMIC_ACQUIRE);
         if (ld_l2(&S.g[s].key) != key) continue;
         const int64_t st0 = S.g[s].start, en0 = S.wend[s];
-        if (!(st0 <= we && en0 >= ws)) continue;
+        // (or the same window: a wrapped window, we < ws, does not intersect its equal, but the MergingWindowSet's
+        // mapping is keyed by the window and the two share one list)
+        if (!((st0 <= we && en0 >= ws) || (st0 == ws && en0 == we))) continue;
         if (nm < SL_MAXM) m[nm] = (int32_t)s;
         nm++;
       }
@@ -2157,6 +2174,12 @@ int cf_watermark(fw_list* op, int64_t wm) {
   return maybe_compact(op);
 }
 
+int runaway_error(fw_list* op) {
+  return set_err(op, FW_ERR_TIME_RANGE,
+                 "Record with a timestamp just above Long.MIN_VALUE + size: the walk of "
+                 "SlidingEventTimeWindows.assignWindows wraps below Long.MIN_VALUE and the reference itself does not "
+                 "return on it.  Nothing of the push was taken.");
+}
 int push_device(fw_list* op, const int64_t* key, const int64_t* ts, const int64_t* val, const int32_t* kh, int64_t n) {
   if (n == 0) return FW_OK;
   if (n > op->max_batch) return set_err(op, FW_ERR_ARG, "batch of %lld records exceeds max_batch %lld", (long long)n,
@@ -2187,6 +2210,7 @@ int push_device(fw_list* op, const int64_t* key, const int64_t* ts, const int64_
                    "'ProcessingTime', or did you forget to call 'DataStream.assignTimestampsAndWatermarks(...)'?");
   if (op->h_ctr->flags & LF_KEY_GROUP)
     return set_err(op, FW_ERR_KEY_GROUP, "a key of the batch is outside the handle's KeyGroupRange");
+  if (op->h_ctr->flags & LF_RANGE) return runaway_error(op);  // (nothing of the push was appended)
   const int64_t E = total;
   // room: the log, a row per possibly firing entry
   LRET(grow_log(op, E));
@@ -2268,7 +2292,8 @@ int fw_list_create(const fw_list_config* cfg, fw_list** out) {
   op->c = LCfg{c.assigner, c.value_type, c.key_kind, c.trigger, c.purging, c.evictor, c.evict_after, c.side_output,
                c.emit_contents, mp, kg0, kg1 - kg0 + 1, c.size, c.slide, c.offset, c.allowed_lateness,
                c.trigger_count, c.evict_count, c.delta_threshold,
-               c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME ? c.trigger_interval : 0};
+               c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME ? c.trigger_interval : 0,
+               c.assigner == FW_SLIDING ? c.size / c.slide + (c.size % c.slide != 0) + 1 : 1};
   op->device = c.device;
   if (hipSetDevice(c.device) != hipSuccess) return fail(FW_ERR_HIP, "hipSetDevice failed");
   if (hipStreamCreateWithFlags(&op->stream, hipStreamNonBlocking) != hipSuccess)
@@ -2369,6 +2394,8 @@ int fw_list_push_batch(fw_list* op, const int64_t* key, const int64_t* ts, const
                        int64_t n) {
   if (!op || n < 0 || (n && (!key || !ts || !val))) return set_err(op, FW_ERR_ARG, "invalid arguments");
   (void)hipSetDevice(op->device);
+  for (int64_t i = 0; i < n; i++)  // host columns: refused before anything is copied or counted
+    if (ts[i] != LMIN && runaway(op->c, ts[i])) return runaway_error(op);
   for (int64_t o = 0; o < n; o += op->max_batch) {
     const int64_t m = std::min(op->max_batch, n - o);
     LHIP(op, hipMemcpyAsync(op->in_key, key + o, (size_t)m * 8, hipMemcpyHostToDevice, op->stream));

@@ -31,6 +31,7 @@
 
 #include "../../include/flink_window.h"
 #include "fw_internal.h"
+#include "fw_range.h"
 
 namespace {
 
@@ -125,6 +126,8 @@ struct fw_op {
   int64_t dig_stride = 0;    // words per row of DevRows::dig (t-digest export: 1 + delta; FW_AGG_ROW: 1 + aggregates)
   int64_t* iota = nullptr;   // FW_AGG_ROW: 0, 1, ... (a record's value is its index in the push)
   int32_t* d_disp = nullptr;  // panes: the displaced-record check's flag (refuse_displaced)
+  uint32_t range_seen = 0;     // Status::range_errors as last settled (the device only adds to it)
+  int64_t range_pending = 0;   // refused device-column records not yet reported (settle)
 
   DevRows out{};
   DevSide side{};
@@ -523,10 +526,23 @@ int log_r_for(const fw_op* op, int64_t need) {
   return log_r;
 }
 
+int time_range_error(fw_op* op, int64_t bad);
+int settle_quiet(fw_op* op);
+// settle, then report the device-column records refused since the last report (FW_ERR_TIME_RANGE: they were left out,
+// everything else was taken, the operator goes on).  The calls that settle in the middle of their own work (a push
+// that queued its batch-only kernels early, a partials push) use settle_quiet, so the error of an earlier push never
+// cuts a later one short: it is returned by the next call that ends in a settle.
+int settle(fw_op* op) {
+  if (int rc = settle_quiet(op)) return rc;
+  if (!op->range_pending) return FW_OK;
+  const int64_t bad = op->range_pending;
+  op->range_pending = 0;
+  return time_range_error(op, bad);
+}
 // Wait for the queued sequence and settle it (see the file comment).  Kernels queued after the
 // snapshot (the next push's classify / scan / scatter) may still be running: they use the other
 // scratch set and write no status field that is rewritten here.
-int settle(fw_op* op) {
+int settle_quiet(fw_op* op) {
   if (!op->unsynced) return FW_OK;
   HIP_OR_RETURN(op, hipEventSynchronize(op->snap));
   if (!op->prof_pending.empty()) prof_collect(op);
@@ -664,6 +680,10 @@ int settle(fw_op* op) {
     return set_err(op, FW_ERR_NO_TIMESTAMP,
                    "Record has Long.MIN_VALUE timestamp (= no timestamp marker). Is the time characteristic set to "
                    "'ProcessingTime', or did you forget to call 'DataStream.assignTimestampsAndWatermarks(...)'?");
+  // device columns refused for their timestamp: the kernels only ever add to the count (a later push's classify may
+  // be queued or running: the host writes nothing back), the host keeps what it has seen and reports the rest
+  op->range_pending += (uint32_t)s.range_errors - op->range_seen;
+  op->range_seen = (uint32_t)s.range_errors;
   if (s.flags & FW_STATUS_MERGE_LATE)
     return set_err(op, FW_ERR_UNSUPPORTED,
                    "The end timestamp of an event-time window cannot become earlier than the current watermark by "
@@ -699,7 +719,7 @@ int maybe_restart_rows(fw_op* op) {
 // FW_COUNT: count windows fire while the batch is processed; no state table, timers or suspension
 int push_count(fw_op* op, const int64_t* key, const int64_t* val, const int32_t* kh, int64_t n) {
   int rc;
-  if ((rc = settle(op)) || (rc = maybe_restart_rows(op))) return rc;
+  if ((rc = settle_quiet(op)) || (rc = maybe_restart_rows(op))) return rc;
   const int64_t rows = (int64_t)op->h_status->out_rows;
   // a key fires at most ceil(r / slide) times for its r elements of the batch
   const int64_t most = std::min<int64_t>(n, n / op->cw.slide + std::min<int64_t>(n, op->cw.max_keys));
@@ -715,6 +735,45 @@ int push_count(fw_op* op, const int64_t* key, const int64_t* val, const int32_t*
 }
 
 hipStream_t input_stream_of(const fw_op* op);  // the stream device pushes read their columns on
+// ---- timestamps at the ends of the long range (DESIGN.md "Event-time arithmetic").  The operators follow the
+// reference's wrapping longs, with three refusals (FW_ERR_TIME_RANGE), the conditions of classify's CLS_RANGE:
+//  * sliding windows kept as panes: a record whose newest window's end, or whose ts - offset + slide, wraps past
+//    Long.MAX_VALUE, or that lies within size + 2 slide of Long.MIN_VALUE (k_fire_panes takes window ends in the
+//    order of the panes' starts);
+//  * every sliding operator: the runaway set just above Long.MIN_VALUE + size, on which the reference's own walk
+//    wraps below Long.MIN_VALUE and runs for about 2^64 / slide steps;
+//  * sliding t-digest windows: a record with several windows of which one's end wraps (the t-digest takes a record's
+//    windows that are not late as its newest ones);
+//  * a pre-shuffle combiner of tumbling windows: the extraction, once a record at or above its window's end was taken
+//    (FW_STATUS_ABOVE_WINDOW; the receiver would count late records by their window's start).
+// Host columns are checked here before anything is copied or queued: the push is refused whole, state, counters and
+// pending rows are those before the call.  Device columns are not read by the host (no stream synchronisation per
+// push): classify leaves such records out and counts them, and the call that settles the push returns the error; the
+// push's other records are taken.  Either way the operator goes on.
+bool time_range_record(const DevCfg& c, int64_t ts) {  // (the arithmetic: fw_range.h, run under the sanitizers)
+  return fw_time_range_record(fw_range_cfg{c.size, c.slide, c.offset, c.wpr, c.panes != 0, c.agg == FW_AGG_TDIGEST}, ts);
+}
+int time_range_error(fw_op* op, int64_t bad) {
+  return set_err(op, FW_ERR_TIME_RANGE,
+                 "%lld record(s) with a timestamp at an end of the long range that this operator does not take: %s",
+                 (long long)bad,
+                 op->dc.panes ? "sliding windows kept as panes refuse a record whose window end wraps past "
+                                "Long.MAX_VALUE or that lies within size + 2 slide of Long.MIN_VALUE (create the "
+                                "operator with no_panes for such timestamps)"
+                              : "the reference's own sliding assigner does not return on a timestamp just above "
+                                "Long.MIN_VALUE + size, and a sliding t-digest does not take a record with several "
+                                "windows of which one's end wraps past Long.MAX_VALUE");
+}
+int refuse_time_range_host(fw_op* op, const int64_t* ts, int64_t n) {
+  const DevCfg& c = op->dc;
+  if (op->cfg.assigner != FW_SLIDING) return FW_OK;
+  int64_t lo, hi;  // only a timestamp within size + 2 slide of an end can be one
+  fw_range_guards(c.size, c.slide, &lo, &hi);
+  int64_t bad = 0;
+  for (int64_t i = 0; i < n; i++)
+    if ((ts[i] <= lo || ts[i] >= hi) && ts[i] != INT64_MIN) bad += time_range_record(c, ts[i]);
+  return bad ? time_range_error(op, bad) : FW_OK;
+}
 // ---- displaced records (DESIGN.md "Event-time arithmetic"): ts - offset + slide < 0 off the slide grid.  The reference
 // gives such a record size / slide + 1 windows, and the pane that would hold it reaches only size / slide of them,
 // so an operator that keeps panes refuses the whole push before anything of it is queued or copied: the state, the
@@ -773,7 +832,7 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
   // output (the scatter appends late records to the side buffer, whose capacity and counters the
   // settle below must see unchanged)
   const bool early = op->unsynced && !c.side_output;
-  if (!early && (rc = settle(op))) return rc;
+  if (!early && (rc = settle_quiet(op))) return rc;
   if (!early && c.side_output) {
     const int64_t rows = (int64_t)op->h_status->side_rows;
     if ((rc = ensure_side_capacity(op, rows + n, rows))) return rc;
@@ -788,14 +847,7 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
   if (c.compact) {
     // compact records: window deltas count from 2^(log_s - 1) windows (or panes) before the watermark's,
     // so the batch's windows on both sides of the watermark fit; no base for a watermark near Long.MIN_VALUE
-    const __int128 u = c.slide, w = op->wm, off = c.offset;
-    __int128 q = (w - off) / u;
-    if ((w - off) % u < 0) q -= 1;  // floor
-    const __int128 base = q * u + off - ((__int128)1 << (c.log_s - 1)) * u;
-    if (base < (__int128)INT64_MIN || base > (__int128)INT64_MAX)
-      c.compact = 0;
-    else
-      c.cbase = (int64_t)base;
+    if (!fw_compact_base(op->wm, c.offset, c.slide, c.log_s, &c.cbase)) c.compact = 0;
   }
   const bool single = S.rsv && !op->rsv_off && op->rcap > 0 && fwdev::rsv_eligible(c);
   // narrow records: integer fields only (a narrow value is an int32), compact windows from the watermark's on
@@ -877,7 +929,7 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
     else
       HIP_OR_RETURN(op, hipMemsetAsync(S.rown, 0, (size_t)n, op->stream));
   }
-  if (early && (rc = settle(op))) return rc;
+  if (early && (rc = settle_quiet(op))) return rc;
   if ((rc = maybe_restart_rows(op))) return rc;
   // the ordered path checks its room per chunk and suspends when it runs out; one chunk always fits
   const int64_t rows = (int64_t)op->h_status->out_rows;
@@ -986,7 +1038,7 @@ uint64_t combine_config_tag(const fw_config& c) {
 int push_partials(fw_op* op, const PartialCols& in, int64_t n, const uint32_t* hregs = nullptr,
                   const uint32_t* hoff = nullptr) {
   int rc;
-  if ((rc = settle(op)) || (rc = maybe_restart_rows(op))) return rc;
+  if ((rc = settle_quiet(op)) || (rc = maybe_restart_rows(op))) return rc;
   const int nxt = op->last_sc ^ 1;
   Scratch& S = op->sc[nxt];
   if (!S.pparts) HIP_OR_RETURN(op, dmalloc(&S.pparts, (size_t)op->max_batch));
@@ -1570,6 +1622,7 @@ int fw_push_batch(fw_op* op, const int64_t* key, const int64_t* ts, const void* 
   if (op->cfg.key_kind == FW_KEY_HASHED && n > 0 && !key_hash)
     return set_err(op, FW_ERR_ARG, "key_hash required for FW_KEY_HASHED");
   HIP_OR_RETURN(op, hipSetDevice(op->device));
+  if (int rc = refuse_time_range_host(op, ts, n)) return rc;  // (first: at the ends of the range the remainder's sign says nothing)
   if (int rc = refuse_displaced_host(op, ts, n)) return rc;
   for (int64_t b = 0; b < n; b += op->max_batch) {
     const int64_t m = std::min(op->max_batch, n - b);
@@ -1636,6 +1689,7 @@ int fw_push_row_batch(fw_op* op, const int64_t* key, const int64_t* ts, const in
   if (op->cfg.key_kind == FW_KEY_HASHED && n > 0 && !key_hash)
     return set_err(op, FW_ERR_ARG, "key_hash required for FW_KEY_HASHED");
   HIP_OR_RETURN(op, hipSetDevice(op->device));
+  if (int rc = refuse_time_range_host(op, ts, n)) return rc;
   for (int64_t b = 0; b < n; b += op->max_batch) {
     const int64_t m = std::min(op->max_batch, n - b);
     HIP_OR_RETURN(op, hipMemcpyAsync(op->in_key, key + b, m * 8, hipMemcpyHostToDevice, op->stream));
@@ -1701,7 +1755,7 @@ int fw_advance_watermark(fw_op* op, int64_t wm, int64_t* n_pending) {
   if (!op->unsynced) {
     const int64_t rows = (int64_t)op->h_status->out_rows;
     if ((rc = ensure_out_capacity(op, rows + op->table_slots, rows))) return rc;
-  } else if (op->fire_unsettled && (rc = settle(op))) {
+  } else if (op->fire_unsettled && (rc = settle_quiet(op))) {
     return rc;  // two watermarks in one sequence: the second needs the first's row count
   }
   timed(op, K_FIRE, [&] { fwdev::launch_fire(op->dc, wm, op->tb, op->out, op->d_status, op->stream); });
@@ -1900,6 +1954,10 @@ static int fw_combine_extract_device_any(fw_op* op, int32_t world, fw_partials* 
   HIP_OR_RETURN(op, hipSetDevice(op->device));
   int rc = fw_synchronize(op);
   if (rc) return rc;
+  if (op->h_status->flags & FW_STATUS_ABOVE_WINDOW)
+    return set_err(op, FW_ERR_TIME_RANGE,
+                   "the combiner took a record that lies at or above its window's end (the end, or ts - offset + size, "
+                   "wrapped past Long.MAX_VALUE): the receiver would count late records by the window's start");
   const DevCfg& c = op->dc;
   if (!op->xoffs) {
     HIP_OR_RETURN(op, dmalloc(&op->xoffs, (size_t)c.P + 1));
@@ -2038,7 +2096,7 @@ int fw_push_hll_partials_device(fw_op* op, const fw_partials* in, int64_t n, con
   HIP_OR_RETURN(op, hipSetDevice(op->device));
   int rc;
   // the previous push settled first: a resumed merge of it reruns its register raise with the offsets it had
-  if ((rc = settle(op))) return rc;
+  if ((rc = settle_quiet(op))) return rc;
   if ((rc = grow_u32(op, &op->hoff, &op->hoff_tmp, &op->hoff_cap, n + 1))) return rc;
   const PartialCols all{in->key, in->start, in->cnt, in->sum, in->min, in->max};
   fwdev::launch_hll_reg_offsets(all, n, op->hoff, op->hoff_tmp, op->stream);
@@ -2827,7 +2885,7 @@ int fw_keyby_combine_push_device(fw_comm* c, fw_op* comb, fw_op* op, const int64
   int rc;
   // HyperLogLog: a merge of the previous batch that suspended reruns its register raise from c->pr / c->rr when it is
   // settled, so it is settled before this batch reallocates those buffers or receives into them
-  if (hll && (rc = settle(op))) return rc;
+  if (hll && (rc = settle_quiet(op))) return rc;
   // the batch into the combiner, ordered after the columns' producer (the caller's fw_stream(op) order)
   hipEvent_t ready = nullptr;
   HIP_OR_RETURN(op, hipEventCreateWithFlags(&ready, hipEventDisableTiming));

@@ -39,6 +39,22 @@ extern "C" {
                                     off the slide grid, to which the reference assigns size / slide + 1 windows
                                     (Java's truncating % in TimeWindow.getWindowStartWithOffset).  The whole push is
                                     refused and nothing changed; fw_config::no_panes keeps windows, which take it */
+#define FW_ERR_TIME_RANGE (-9)   /* a timestamp at an end of the long range that the operator does not take.  Timestamps
+                                    and window bounds are Java longs and wrap as the reference's do; refused are
+                                    (a) by every sliding operator, a timestamp just above Long.MIN_VALUE + size on
+                                    which SlidingEventTimeWindows.assignWindows' walk wraps below Long.MIN_VALUE (the
+                                    reference itself does not return on it); (b) by sliding windows kept as panes, a
+                                    record whose window end wraps past Long.MAX_VALUE or that lies within
+                                    size + 2 slide of Long.MIN_VALUE (fw_config::no_panes takes them); (c) by sliding
+                                    t-digest windows, a record with several windows of which one's end wraps; (d) by
+                                    fw_combine_extract_device of a tumbling combiner, every extraction once the
+                                    combiner took a record at or above its window's end (the end, or
+                                    ts - offset + size, wrapped).  Host columns, and every push of the window-contents (list)
+                                    operator: the whole push is refused and nothing changed.  Device columns of
+                                    fw_push_batch_device: those records are left out, the others taken, and the next
+                                    call that ends by settling the operator (fw_synchronize, fw_advance_watermark with
+                                    a count, fw_pending, a drain, ...) returns the code once, for every push since
+                                    the last report; a push queued behind a refused one is taken in full.  The operator goes on */
 
 /* ---- assigner, value and key kinds ---- */
 #define FW_TUMBLING 0 /* api/windowing/assigners/TumblingEventTimeWindows.java:53-73 */

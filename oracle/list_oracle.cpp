@@ -212,7 +212,12 @@ struct ListOracle {
       return;
     }
     const int64_t last = window_start(ts, cfg.offset, cfg.slide);  // SlidingEventTimeWindows.java:67-81
-    for (int64_t s = last; s > jsub(ts, cfg.size); s = jsub(s, cfg.slide)) out.push_back(W{s, jadd(s, cfg.size)});
+    // (OR_ERR_RUNAWAY, window_oracle.h: the walk wrapped below Long.MIN_VALUE, the reference does not return)
+    const uint64_t cap = (uint64_t)cfg.size / (uint64_t)cfg.slide + ((uint64_t)cfg.size % (uint64_t)cfg.slide != 0) + 1;
+    for (int64_t s = last; s > jsub(ts, cfg.size); s = jsub(s, cfg.slide)) {
+      if (out.size() == cap) throw OpErr{OR_ERR_RUNAWAY};
+      out.push_back(W{s, jadd(s, cfg.size)});
+    }
   }
 
   // DeltaEvictor's built-in DeltaFunction: last.field - e.field in the field's Java arithmetic

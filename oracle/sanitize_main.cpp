@@ -4,13 +4,16 @@
 // It drives the oracle through every operator shape (tumbling / sliding / sessions, lateness, purging,
 // side output, first-element, minBy/maxBy, HyperLogLog, t-digest, count windows, the multi-threaded
 // baseline) on a seeded stream with extreme keys and timestamps, and checks the host-side arithmetic the
-// library shares with the device code (make_div_inv, flink_amd/csrc/fw_internal.h) against 128-bit division.
+// library shares with the device code (make_div_inv, flink_amd/csrc/fw_internal.h) against 128-bit division, and
+// at both ends of the long range the window start, the host's FW_ERR_TIME_RANGE refusals and the compact records' base
+// (flink_amd/csrc/fw_range.h) against 128-bit restatements and the oracle.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../flink_amd/csrc/fw_internal.h"
+#include "../flink_amd/csrc/fw_range.h"
 #include "window_oracle.h"
 
 static uint64_t sm(uint64_t z) {
@@ -87,6 +90,140 @@ static int check_window_start() {
   return bad;
 }
 
+// ---- the ends of the long range (DESIGN.md "Event-time arithmetic"): every timestamp within `span` of Long.MAX_VALUE
+// and of Long.MIN_VALUE
+static const int64_t END_SPAN = 6000;
+template <class F>
+static void for_end_timestamps(F f) {
+  for (int64_t d = 0; d <= END_SPAN; d++) {
+    f(INT64_MAX - d);
+    f(INT64_MIN + d);
+  }
+}
+// the reciprocal remainder and the window start where ts - offset, + size or the start itself wraps
+static int check_window_start_at_the_ends() {
+  int bad = 0;
+  const int64_t cfgs[][2] = {{1000, 0}, {1000, 1}, {1000, 999}, {1000, 808}, {1000, 308}, {2500, 0}, {500, 308},
+                             {700, 1}, {7, 3}, {1000003, 17}, {(1ll << 40) + 15, 12345}, {(1ll << 61) + 1, 5}};
+  for (auto& c : cfgs) {
+    const int64_t d = c[0], off = c[1];
+    uint64_t m;
+    int32_t l;
+    make_div_inv((uint64_t)d, &m, &l);
+    for_end_timestamps([&](int64_t ts) {
+      const int64_t t = fw_wadd(fw_wsub(ts, off), d);
+      const uint64_t u = t < 0 ? (uint64_t)0 - (uint64_t)t : (uint64_t)t;
+      const uint64_t r = u - div_inv_host(u, m, l) * (uint64_t)d;
+      const int64_t rem = t < 0 ? -(int64_t)r : (int64_t)r;
+      if (rem != (int64_t)((__int128)t % (__int128)d) || fw_wsub(ts, rem) != oracle_window_start(ts, off, d)) bad++;
+    });
+  }
+  return bad;
+}
+// SlidingEventTimeWindows.assignWindows on 128-bit ints that are wrapped to a long after every step, for at most
+// `cap` + 1 windows: the count, whether the newest end wrapped, whether the walk ran past the cap
+struct RefWalk {
+  int k;
+  bool newest_wraps, runaway;
+};
+static int64_t wrap128(__int128 x) { return (int64_t)(uint64_t)(unsigned __int128)x; }
+static RefWalk ref_walk(int64_t ts, int64_t size, int64_t slide, int64_t off, int cap) {
+  const int64_t t = wrap128((__int128)wrap128((__int128)ts - off) + slide);
+  const int64_t last = wrap128((__int128)ts - (int64_t)((__int128)t % slide)), lo = wrap128((__int128)ts - size);
+  RefWalk w{0, (__int128)last + size > (__int128)INT64_MAX, false};
+  for (int64_t s = last; s > lo; s = wrap128((__int128)s - slide)) {
+    if (w.k == cap) {
+      w.runaway = true;
+      break;
+    }
+    w.k++;
+  }
+  return w;
+}
+// the host's refusals (fw_range.h: fw_time_range_record, fw_range_guards, fw_sliding_runaway) against that walk and
+// against the oracle, which returns OR_ERR_RUNAWAY on exactly the runaway set
+static int check_time_range() {
+  int bad = 0;
+  const int64_t cfgs[][3] = {{2500, 1000, 0}, {2500, 1000, 808}, {2500, 1000, 308}, {3000, 1000, 0}, {3000, 500, 1},
+                             {700, 1000, 0}, {1000, 1000, 999}, {7, 3, 2}};
+  for (auto& c : cfgs) {
+    const int64_t size = c[0], slide = c[1], off = c[2];
+    const int cap = (int)(size / slide + (size % slide != 0) + 1);
+    int64_t glo, ghi;
+    fw_range_guards(size, slide, &glo, &ghi);
+    oracle_cfg oc{};
+    oc.assigner = OR_SLIDING;
+    oc.size = size;
+    oc.slide = slide;
+    oc.offset = off;
+    int n_run = 0;
+    for_end_timestamps([&](int64_t ts) {
+      if (ts == INT64_MIN) return;
+      const RefWalk w = ref_walk(ts, size, slide, off, cap);
+      const fw_range_cfg win{size, slide, off, cap, false, false}, td{size, slide, off, cap, false, true};
+      const fw_range_cfg pane{size, slide, off, cap, true, false};
+      if (fw_time_range_record(win, ts) != w.runaway) bad++;
+      if (fw_sliding_runaway(size, slide, off, cap, ts) != w.runaway) bad++;
+      if (fw_time_range_record(td, ts) != (w.runaway || (w.k > 1 && w.newest_wraps))) bad++;
+      const bool t_wraps = (__int128)wrap128((__int128)ts - off) + slide > (__int128)INT64_MAX;
+      const bool bottom = (__int128)ts - size - 2 * (__int128)slide < (__int128)INT64_MIN;
+      if (fw_time_range_record(pane, ts) != (w.newest_wraps || t_wraps || bottom)) bad++;
+      // nothing between the guards is ever refused, so whatever is refused lies at or beyond one of them
+      if ((fw_time_range_record(win, ts) || fw_time_range_record(td, ts) || fw_time_range_record(pane, ts)) &&
+          ts > glo && ts < ghi)
+        bad++;
+      if (w.runaway || (uint64_t)ts - (uint64_t)INT64_MIN == (uint64_t)(size - 1) || ts == INT64_MAX) {  // the oracle agrees on the set and its edges
+        void* op = oracle_create(&oc);
+        const int64_t k = 1, v = 1;
+        if ((oracle_process(op, &k, &ts, &v, 1) == OR_ERR_RUNAWAY) != w.runaway) bad++;
+        oracle_destroy(op);
+      }
+      n_run += w.runaway;
+    });
+    if (size == 2500 && off == 0 && n_run != 808) bad++;  // ts - Long.MIN_VALUE in [2500, 3307]
+    for (int i = 0; i < 2000; i++) {  // and timestamps anywhere else are taken
+      const int64_t ts = (int64_t)sm((uint64_t)i * 7919u + (uint64_t)size) >> (i % 30);
+      if (ts > glo && ts < ghi && (fw_time_range_record(fw_range_cfg{size, slide, off, cap, true, true}, ts) ||
+                                   fw_sliding_runaway(size, slide, off, cap, ts)))
+        bad++;
+    }
+  }
+  // sizes for which size + 2 slide leaves the long range: the guards saturate, nothing overflows
+  for (int64_t size : {(int64_t)((1ll << 62) + 1), (int64_t)INT64_MAX}) {
+    int64_t glo, ghi;
+    fw_range_guards(size, size, &glo, &ghi);
+    if (glo < -1 || ghi > 0) bad++;
+    for (int64_t ts : {(int64_t)(INT64_MIN + 1), (int64_t)-1, (int64_t)0, (int64_t)INT64_MAX}) {
+      (void)fw_time_range_record(fw_range_cfg{size, size, 0, 2, true, false}, ts);
+      (void)fw_sliding_runaway(size, size, 0, 2, ts);
+    }
+  }
+  return bad;
+}
+// the compact records' base with watermarks at both ends: a base is on the grid, 2^(log_s - 1) steps below the
+// watermark's grid point, and refused exactly when that point leaves the long range
+static int check_compact_base() {
+  int bad = 0;
+  const int64_t cfgs[][2] = {{1000, 0}, {1000, 808}, {1000, 999}, {100, 1}, {(1ll << 40) + 15, 7}, {(1ll << 62) + 1, 0}};
+  for (auto& c : cfgs) {
+    const int64_t step = c[0], off = c[1];
+    for (int log_s : {1, 3, 8, 12}) {
+      auto one = [&](int64_t wm) {
+        int64_t base = 0;
+        const bool ok = fw_compact_base(wm, off, step, log_s, &base);
+        __int128 g = (__int128)wm - off;  // the watermark's grid point, by floor division on 128 bits
+        g = g - ((g % step) + step) % step + off;
+        const __int128 want = g - ((__int128)1 << (log_s - 1)) * step;
+        const bool fits = want >= (__int128)INT64_MIN && want <= (__int128)INT64_MAX;
+        if (ok != fits || (ok && (__int128)base != want)) bad++;
+      };
+      for_end_timestamps(one);
+      for (int64_t wm : {(int64_t)0, (int64_t)-1, (int64_t)1, off, (int64_t)(off - 1)}) one(wm);
+    }
+  }
+  return bad;
+}
+
 static void run(oracle_cfg cfg, int n, uint64_t seed) {
   void* op = oracle_create(&cfg);
   std::vector<int64_t> k(n), t(n), v(n);
@@ -132,6 +269,14 @@ int main() {
   const int bad_ws = check_window_start();
   if (bad_ws) {
     fprintf(stderr, "window start through the reciprocal: %d wrong\n", bad_ws);
+    return 1;
+  }
+  const int bad_ends = check_window_start_at_the_ends();
+  const int bad_range = check_time_range();
+  const int bad_base = check_compact_base();
+  if (bad_ends || bad_range || bad_base) {
+    fprintf(stderr, "the ends of the long range: %d wrong window starts, %d wrong refusals, %d wrong compact bases\n",
+            bad_ends, bad_range, bad_base);
     return 1;
   }
   oracle_cfg base{};

@@ -706,7 +706,13 @@ class WindowOperatorOracle {
     }
     // SlidingEventTimeWindows.java:67-81
     int64_t last = window_start(ts, cfg.offset, cfg.slide);
-    for (int64_t s = last; s > jsub(ts, cfg.size); s = jsub(s, cfg.slide)) out.push_back(TW{s, jadd(s, cfg.size)});
+    // (a walk that has not ended after ceil(size / slide) + 1 windows has wrapped below Long.MIN_VALUE: the
+    // reference's own loop then runs for about 2^64 / slide steps)
+    const uint64_t cap = (uint64_t)cfg.size / (uint64_t)cfg.slide + ((uint64_t)cfg.size % (uint64_t)cfg.slide != 0) + 1;
+    for (int64_t s = last; s > jsub(ts, cfg.size); s = jsub(s, cfg.slide)) {
+      if (out.size() == cap) throw OpError{OR_ERR_RUNAWAY};
+      out.push_back(TW{s, jadd(s, cfg.size)});
+    }
   }
 
   // ------------------------------------------------ MergingWindowSet.java:150-225 (+ TimeWindow.mergeWindows)

@@ -44,6 +44,9 @@ enum {
   OR_ERR_NO_TIMESTAMP = -1,   /* Long.MIN_VALUE timestamp: TumblingEventTimeWindows.java:69-71 */
   OR_ERR_MERGE_LATE = -2,     /* UnsupportedOperationException, WindowOperator.java:313-317 */
   OR_ERR_ILLEGAL_STATE = -3,  /* IllegalStateException, MergingWindowSet.java:127 / WindowOperator.java:355 */
+  OR_ERR_RUNAWAY = -4,        /* a sliding timestamp just above Long.MIN_VALUE + size: the walk of
+                                 SlidingEventTimeWindows.java:71-75 wraps below Long.MIN_VALUE and the reference does not
+                                 return (about 2^64 / slide windows); nothing of the record is taken */
 };
 
 typedef struct {

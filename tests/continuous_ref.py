@@ -60,10 +60,14 @@ def hashset_order(windows):
     return [w for _, _, w in sorted((bucket(w), i, w) for i, w in enumerate(windows))]
 
 
+class TimerRunaway(RuntimeError):
+    """the reference would not return in any useful time on this stream (ContinuousRef timer_cap, the sliding walk)"""
+
+
 class ContinuousRef:
     def __init__(self, assigner="tumbling", size=0, slide=0, offset=0, gap=0, lateness=0, trigger="event_time",
                  interval=0, purging=False, evictor="none", evict_after=False, evict_arg=0, side_output=False,
-                 value_type="i64"):
+                 value_type="i64", timer_cap=None):
         assert assigner in ("tumbling", "sliding", "global", "session")
         assert trigger in ("event_time", "continuous") and evictor in ("none", "count", "time")
         assert value_type in ("i64", "f64") and (trigger != "continuous" or interval >= 1)
@@ -71,6 +75,11 @@ class ContinuousRef:
         self.lateness, self.trigger, self.interval, self.purging = lateness, trigger, interval, purging
         self.evictor, self.evict_after, self.evict_arg = evictor, evict_after, evict_arg
         self.side_output, self.value_type = side_output, value_type
+        # the most timers one watermark may fire (None: no bound).  A ContinuousEventTimeTrigger whose first timer
+        # ts - ts % interval + interval wraps past Long.MAX_VALUE starts its chain at the bottom of the range, and
+        # unless the window's cleanup timer comes first the chain walks up to the watermark, 2^64 / interval steps in
+        # the reference too: TimerRunaway instead of not returning
+        self.timer_cap = timer_cap
         self.wm = LMIN
         self.epoch = 0
         self.ordinal = 0
@@ -101,6 +110,8 @@ class ContinuousRef:
         last = jwrap(ts - jrem(jwrap(jwrap(ts - self.offset) + self.slide), self.slide))
         out, s = [], last
         while s > jwrap(ts - self.size):
+            if len(out) == -(-self.size // self.slide) + 1:  # (the walk wrapped below Long.MIN_VALUE: window_ref.Runaway)
+                raise TimerRunaway(f"sliding walk of ts {ts} does not end")
             out.append((s, jwrap(s + self.size)))
             s = jwrap(s - self.slide)
         return out
@@ -307,10 +318,14 @@ class ContinuousRef:
         wm = int(wm)
         if wm > self.wm:
             self.wm = wm
+            fired = 0
             while self.heap and self.heap[0][0] <= wm:
                 t, key, w = heapq.heappop(self.heap)
                 if (t, key, w) not in self.timers:
                     continue
+                fired += 1
+                if self.timer_cap is not None and fired > self.timer_cap:
+                    raise TimerRunaway(f"watermark {wm} fires more than {self.timer_cap} timers")
                 self.timers.discard((t, key, w))
                 self._timer(t, key, w)
         self.epoch += 1

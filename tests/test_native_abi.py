@@ -62,6 +62,14 @@ def test_create_rejects_invalid_config(kw, msg):
     assert msg in m
 
 
+def test_error_codes_match_header():
+    # every FW_ERR_* of the header, mirrored in flink_amd/_native.py with the same value
+    codes = dict(re.findall(r"^#define (FW_ERR_\w+) \((-\d+)\)", open(HEADER).read(), flags=re.M))
+    assert len(codes) >= 9 and codes["FW_ERR_TIME_RANGE"] == "-9"
+    for name, value in codes.items():
+        assert getattr(N, name) == int(value), name
+
+
 def test_kernel_names():
     names = [N.lib().fw_kernel_name(i).decode() for i in range(N.FW_NUM_KERNELS)]
     assert names == ["k_classify_hist", "k_scan", "k_scatter", "k_aggregate", "k_slow", "k_fire", "k_tdigest"]

@@ -35,17 +35,41 @@ def tumbling_windows(ts, size, offset=0):
     return [(s, wrap64(s + size))]
 
 
-def sliding_windows(ts, size, slide, offset=0):
-    """SlidingEventTimeWindows.assignWindows (api/windowing/assigners/SlidingEventTimeWindows.java:67-81), newest first"""
+class Runaway(ValueError):
+    """a timestamp on which the reference's own loop does not return (sliding_windows)"""
+
+
+def sliding_cap(size, slide):
+    """the most windows a sliding record has, a displaced record's extra one included: ceil(size / slide) + 1"""
+    return -(-size // slide) + 1
+
+
+def sliding_windows(ts, size, slide, offset=0, cap=None):
+    """SlidingEventTimeWindows.assignWindows (api/windowing/assigners/SlidingEventTimeWindows.java:67-81), newest first.
+    The loop is evaluated for at most `cap` windows (default sliding_cap): for a timestamp just above
+    Long.MIN_VALUE + size, `ts - size` does not wrap but the walk down does, past Long.MIN_VALUE to the top of the
+    range, and the reference runs for about 2^64 / slide steps.  Such a timestamp is in the runaway set: Runaway."""
     if ts <= LONG_MIN:
         raise ValueError("Record has Long.MIN_VALUE timestamp (= no timestamp marker).")
+    cap = sliding_cap(size, slide) if cap is None else cap
     out = []
     start = window_start(ts, offset, slide)
     lo = wrap64(ts - size)
     while start > lo:
+        if len(out) == cap:
+            raise Runaway(f"sliding walk of ts {ts} (size {size}, slide {slide}, offset {offset}) passes {cap} windows")
         out.append((start, wrap64(start + size)))
         start = wrap64(start - slide)
     return out
+
+
+def is_runaway(ts, size, slide, offset=0):
+    """ts is in the runaway set of the sliding assigner (size, slide, offset)"""
+    try:
+        sliding_windows(ts, size, slide, offset)
+    except Runaway:
+        return True
+    return False
 
 
 def session_window(ts, gap):
