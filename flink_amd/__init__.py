@@ -23,7 +23,7 @@ def __getattr__(name):
     if name in ("GroupWindowAggregate", "Tumble", "Slide", "Session"):
         from . import table
         return getattr(table, name)
-    if name == "GpuListWindowOperator":
-        from .listwindow import GpuListWindowOperator
-        return GpuListWindowOperator
+    if name in ("GpuListWindowOperator", "SESSION_STATE_DTYPE"):
+        from . import listwindow
+        return getattr(listwindow, name)
     raise AttributeError(name)

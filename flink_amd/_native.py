@@ -105,7 +105,7 @@ FW_EVICT_NONE, FW_EVICT_COUNT, FW_EVICT_TIME, FW_EVICT_DELTA = 0, 1, 2, 3
 class FwListConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "assigner", "value_type", "key_kind", "trigger", "purging", "evictor", "evict_after", "side_output",
-        "emit_contents", "max_parallelism", "key_group_start", "key_group_end", "device", "pad0")] + \
+        "emit_contents", "max_parallelism", "key_group_start", "key_group_end", "device", "merging_state")] + \
         [(n, ctypes.c_int64) for n in ("size", "slide", "offset", "allowed_lateness", "trigger_count",
                                        "evict_count")] + \
         [("delta_threshold", ctypes.c_double), ("expected_elements", ctypes.c_int64), ("max_batch", ctypes.c_int64),
@@ -124,6 +124,11 @@ class FwListElems(ctypes.Structure):
 class FwListState(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("key", "start", "end", "trigger_count", "timer", "n_elems", "ts", "val",
                                                "ordinal")]
+
+
+class FwSessionState(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("key", "start", "end", "state_start", "state_end", "trigger_state",
+                                               "timer", "n_elems", "ts", "val", "ordinal")]
 
 
 # every exported symbol with its ctypes signature (restype, argtypes); mirrors include/flink_window.h
@@ -203,6 +208,10 @@ SIGNATURES = {
                                                   ctypes.c_int64, I64P, I64P]),
     "fw_list_restore_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwListState), ctypes.c_int64,
                                                  ctypes.c_int64]),
+    "fw_list_snapshot_sessions": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwSessionState), ctypes.c_int64,
+                                                 ctypes.c_int64, I64P, I64P]),
+    "fw_list_restore_sessions": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwSessionState), ctypes.c_int64,
+                                                ctypes.c_int64]),
     "fw_count_snapshot_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwListState), ctypes.c_int64,
                                                    ctypes.c_int64, I64P, I64P]),
     "fw_count_restore_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwListState), ctypes.c_int64,

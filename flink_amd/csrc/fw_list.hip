@@ -56,6 +56,11 @@ enum : uint32_t {
   LF_RANGE = 64u  // a sliding timestamp of the runaway set (FW_ERR_TIME_RANGE)
 };
 constexpr uint32_t G_EMPTY = 0u, G_BUSY = 1u, G_LIVE = 2u, G_TOMB = 3u;
+// session windows: a window merged away by a push.  Its slot is not handed out again in that launch: its per-slot
+// columns (wend, whead, ...) are plain stores that stay in the writing XCD's L2, and a thread of another XCD that
+// claimed the slot at once would race them (the key's own thread may: it is the one that wrote them).  The next
+// watermark pass turns it into a tombstone.
+constexpr uint32_t G_DEAD = 4u;
 
 struct LCfg {
   int32_t assigner, vt, key_kind, trigger, purging, evictor, evict_after, side_output, emit, max_par, kg0, nkg;
@@ -94,6 +99,9 @@ struct LState {
   uint32_t* gfpos;
   // session windows (FW_SESSION, fw_list.hip "session windows"): per slot its window end and list head / tail
   int64_t *wend, *whead, *wtail;
+  // merging_state handles only (null otherwise): per slot the MergingWindowSet's state window of the in-flight window
+  // (the namespace its list is kept under) and CountTrigger's "count" ReducingState (GSlot.cnt is the list length)
+  int64_t *wsst, *wsen, *gtc;
   LPay* lpay;  // the elements' payload, one 32-byte sector each (a gather reads one sector per element)
   int32_t* lgid;
   int64_t *rkey, *rstart, *rend, *rcnt, *rsum, *rmin, *rmax, *rfirst, *roff;
@@ -1111,11 +1119,13 @@ __device__ __forceinline__ int64_t sl_timer_of(const LCfg& c, uint32_t fl, int64
 
 // a new window slot for key on its chain (from `from`, a TOMB / EMPTY slot the walk met first): claimed with a CAS
 // (other threads insert other keys), its fields stored write-through, then LIVE (g_find_insert's publication)
-__device__ int32_t sl_insert(const LState& S, int64_t key, int32_t kg, int64_t start, int64_t end, uint32_t from) {
+// own_dead: `from` is a slot this key's thread merged away in this launch (G_DEAD): only that thread may take it again
+__device__ int32_t sl_insert(const LState& S, int64_t key, int32_t kg, int64_t start, int64_t end, uint32_t from,
+                             bool own_dead = false) {
   uint32_t s = from;
   for (uint32_t probes = 0; probes <= S.gmask; probes++, s = (s + 1) & S.gmask) {
     uint32_t cur = __hip_atomic_load(&S.g[s].st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur != G_EMPTY && cur != G_TOMB) continue;
+    if (cur != G_EMPTY && cur != G_TOMB && !(own_dead && probes == 0 && cur == G_DEAD)) continue;
     if (atomicCAS(&S.g[s].st, cur, G_BUSY) != cur) continue;  // (taken meanwhile: it is some key's now)
     __hip_atomic_store(&S.g[s].key, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&S.g[s].start, start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1126,9 +1136,14 @@ __device__ int32_t sl_insert(const LState& S, int64_t key, int32_t kg, int64_t s
     S.whead[s] = -1;
     S.wtail[s] = -1;
     if (S.gfire) S.gfire[s] = LMIN;
+    if (S.wsst) {  // MergingWindowSet.addWindow maps a new window to itself; the trigger's count is null
+      S.wsst[s] = start;
+      S.wsen[s] = end;
+      S.gtc[s] = 0;
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __hip_atomic_store(&S.g[s].st, (uint32_t)G_LIVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == G_TOMB) atomicAdd(&S.ctr->tombs, (unsigned long long)-1ll);
+    if (cur != G_EMPTY) atomicAdd(&S.ctr->tombs, (unsigned long long)-1ll);  // (a dead slot counts as a tombstone)
     return (int32_t)s;
   }
   atomicOr(&S.ctr->flags, LF_MAP_FULL);
@@ -1292,6 +1307,7 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
   long long due = LMAX;
   unsigned long long killed = 0, late = 0, ins = 0, tombs = 0;
   const bool cont = c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME;
+  const bool ctrig = c.trigger == FW_TRIGGER_COUNT;  // (merging_state handles only: S.gtc is there)
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nruns; r += (int64_t)gridDim.x * blockDim.x) {
     int64_t q = prog[r];
     if (q == LMAX) continue;
@@ -1316,6 +1332,7 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
       int32_t m[SL_MAXM];
       int nm = 0;
       uint32_t freeslot = 0xffffffffu, s = home;
+      bool freedead = false;
       for (uint32_t probes = 0; probes <= S.gmask; probes++, s = (s + 1) & S.gmask) {
         const uint32_t st = __hip_atomic_load(&S.g[s].st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (st == G_EMPTY) {
@@ -1324,6 +1341,13 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
         }
         if (st == G_TOMB) {
           if (freeslot == 0xffffffffu) freeslot = s;
+          continue;
+        }
+        if (st == G_DEAD) {  // merged away in this launch: free again for the thread that owned it, this key's
+          if (freeslot == 0xffffffffu && ld_l2(&S.g[s].key) == key) {
+            freeslot = s;
+            freedead = true;
+          }
           continue;
         }
         if (st != G_LIVE) continue;  // (BUSY: another key's window being published)
@@ -1356,7 +1380,7 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
           }
           continue;
         }
-        actual = sl_insert(S, key, kg, ws, we, freeslot == 0xffffffffu ? home : freeslot);
+        actual = sl_insert(S, key, kg, ws, we, freeslot == 0xffffffffu ? home : freeslot, freedead);
         if (actual < 0) break;
         ins++;
       } else {
@@ -1438,8 +1462,12 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
               S.gfire[target] = S.gfire[target] == LMIN ? S.gfire[sl] : min(S.gfire[target], S.gfire[sl]);
               S.gfire[sl] = LMIN;
             }
-            __hip_atomic_store(&S.g[sl].st, (uint32_t)G_TOMB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tombs++;
+            if (S.gtc) {  // CountTrigger.onMerge: the "count" ReducingState merges by Sum; the merged window's is cleared
+              S.gtc[target] += S.gtc[sl];
+              S.gtc[sl] = 0;
+            }
+            __hip_atomic_store(&S.g[sl].st, (uint32_t)G_DEAD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            tombs++;  // (counted as a tombstone from now on: it holds its slot like one)
           }
           int64_t lo = LMAX;
           for (int i = 0; i < n; i++) lo = min(lo, ms[i]);
@@ -1448,7 +1476,7 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
           if (cont)  // ContinuousEventTimeTrigger.onMerge registers the merged fire time only; the merged windows'
                      // own timers belong to windows that are gone (WindowOperator.onEventTime ignores them)
             S.g[target].fl = (S.g[target].fl & ~(GF_TIMER | GF_FPEND)) | (S.gfire[target] != LMIN ? GF_FPEND : 0u);
-          else
+          else if (!ctrig)  // (CountTrigger.onMerge registers no timer and does not fire)
             S.g[target].fl |= GF_TIMER;  // EventTimeTrigger.onMerge registers the merged window's maxTimestamp
           actual = target;
         }
@@ -1460,6 +1488,22 @@ __global__ __launch_bounds__(256) void k_sl_process(LCfg c, LState S, const uint
         S.whead[actual] = q;
       S.wtail[actual] = q;
       S.g[actual].cnt++;
+      if (ctrig) {
+        // CountTrigger.onElement (:47-57): count += 1; at n the count is cleared and the window fires.  The count is
+        // cleared before the emit is attempted, so a resumed firing (prog / pslot) has nothing to count again.  No
+        // timer is registered: the window waits for its cleanup time only.
+        if (++S.gtc[actual] >= c.trig_n) {
+          S.gtc[actual] = 0;
+          if (!sl_emit(c, S, actual, true, &killed)) {
+            prog[r] = q;
+            pslot[r] = actual;
+            break;
+          }
+          if (c.purging) sl_clear(S, actual, &killed);
+        }
+        due = min(due, (long long)sl_cleanup(c, S.wend[actual]));
+        continue;
+      }
       // EventTimeTrigger.onElement: FIRE when the window's maxTimestamp is not after the watermark
       if (sl_max_ts(S.wend[actual]) <= wm) {
         if (!sl_emit(c, S, actual, true, &killed)) {
@@ -1494,6 +1538,7 @@ __global__ __launch_bounds__(256) void k_sl_due(LCfg c, LState S, int64_t wm) {
   long long due = LMAX;
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= (int64_t)S.gmask;
        g += (int64_t)gridDim.x * blockDim.x) {
+    if (S.g[g].st == G_DEAD) S.g[g].st = G_TOMB;
     if (S.g[g].st != G_LIVE) continue;
     const int64_t end = S.wend[g];
     const uint32_t f0 = S.g[g].fl;
@@ -1535,6 +1580,7 @@ __global__ __launch_bounds__(256) void k_sl_fire(LCfg c, LState S) {
     }
     if (f & GF_CLEAN) {
       sl_clear(S, (int32_t)g, &killed);
+      if (S.gtc) S.gtc[g] = 0;  // clearAllState: the trigger's count goes with the window, without a firing
       S.g[g].st = G_TOMB;
       nt++;
     }
@@ -1572,6 +1618,7 @@ __global__ __launch_bounds__(256) void k_sl_cf_fire(LCfg c, LState S, int64_t wm
   long long due = LMAX;
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= (int64_t)S.gmask;
        g += (int64_t)gridDim.x * blockDim.x) {
+    if (S.g[g].st == G_DEAD) S.g[g].st = G_TOMB;
     if (S.g[g].st != G_LIVE) continue;
     const int64_t end = S.wend[g], M = sl_max_ts(end), cl = sl_cleanup(c, end);
     uint32_t fl = S.g[g].fl;
@@ -1628,6 +1675,11 @@ __global__ __launch_bounds__(256) void k_sl_rebuild(LState o, LState S, const in
     S.g[s].fl = o.g[g].fl;
     S.g[s].cnt = o.g[g].cnt;
     if (o.gfire) S.gfire[s] = o.gfire[g];
+    if (o.wsst) {
+      S.wsst[s] = o.wsst[g];
+      S.wsen[s] = o.wsen[g];
+      S.gtc[s] = o.gtc[g];
+    }
     const int64_t h = o.whead[g], t = o.wtail[g];
     S.whead[s] = h >= 0 && remap ? remap[h] : h;
     S.wtail[s] = t >= 0 && remap ? remap[t] : t;
@@ -1652,6 +1704,97 @@ __global__ __launch_bounds__(256) void k_sl_count_state(LCfg c, LState S, unsign
   }
   if (lists) atomicAdd(&out2[0], lists);
   if (timers) atomicAdd(&out2[1], timers);
+}
+
+// ---- session snapshots (merging_state handles): fw_session_state, include/flink_window.h
+// per map slot: 1 when it is an in-flight window of the key group, and its list's length (GSlot.cnt: no list walk)
+__global__ __launch_bounds__(256) void k_ss_flags(LState S, int32_t kg, unsigned long long* __restrict__ wf,
+                                                  unsigned long long* __restrict__ wl) {
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= (int64_t)S.gmask;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    const bool in = S.g[g].st == G_LIVE && S.g[g].kg == kg;
+    wf[g] = in;
+    wl[g] = in ? (unsigned long long)S.g[g].cnt : 0ull;
+  }
+}
+// one thread per window: wf / wl are the inclusive scans of k_ss_flags' columns (the window's row and, less its own
+// length, its elements' offset); its columns, then its list walked into its offset.  win: 8 columns of nw, el: 3 of ne
+__global__ __launch_bounds__(256) void k_ss_write(LCfg c, LState S, int32_t kg, const unsigned long long* __restrict__ wf,
+                                                  const unsigned long long* __restrict__ wl, int64_t nw, int64_t ne,
+                                                  int64_t* __restrict__ win, int64_t* __restrict__ el) {
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= (int64_t)S.gmask;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    if (!(S.g[g].st == G_LIVE && S.g[g].kg == kg)) continue;
+    const int64_t i = (int64_t)wf[g] - 1, n = S.g[g].cnt, off = (int64_t)wl[g] - n;
+    if (i < 0 || i >= nw || n < 0 || off < 0 || off + n > ne) continue;  // (an inconsistent map writes nothing)
+    const uint32_t fl = S.g[g].fl;
+    win[0 * nw + i] = S.g[g].key;
+    win[1 * nw + i] = S.g[g].start;
+    win[2 * nw + i] = S.wend[g];
+    win[3 * nw + i] = S.wsst[g];
+    win[4 * nw + i] = S.wsen[g];
+    win[5 * nw + i] = c.trigger == FW_TRIGGER_COUNT ? S.gtc[g] : S.gfire ? S.gfire[g] : 0;
+    win[6 * nw + i] = ((fl & GF_TIMER) ? 1 : 0) | ((fl & GF_FPEND) ? 2 : 0);
+    win[7 * nw + i] = n;
+    int64_t k = 0;
+    for (int64_t q = S.whead[g]; q >= 0 && k < n; k++) {
+      const LPay p = S.lpay[q];
+      el[0 * ne + off + k] = p.ts;
+      el[1 * ne + off + k] = p.val;
+      el[2 * ne + off + k] = p.ord;
+      q = p.pad;
+    }
+  }
+}
+// restore, the check: a key of the snapshot that has an in-flight window in the handle (its chain from its home slot)
+__global__ __launch_bounds__(256) void k_sr_check(LState S, const int64_t* __restrict__ key, int64_t nw,
+                                                  unsigned int* __restrict__ found) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t s = sl_home(key[i]) & S.gmask;
+    for (uint32_t probes = 0; probes <= S.gmask; probes++, s = (s + 1) & S.gmask) {
+      const uint32_t st = S.g[s].st;
+      if (st == G_EMPTY) break;
+      if (st == G_LIVE && S.g[s].key == key[i]) {
+        atomicOr(found, 1u);
+        break;
+      }
+    }
+  }
+}
+// restore, the apply: one thread per window -- its elements appended to the log at base + eoff[i], linked in list
+// order, and its slot claimed on the key's chain (sl_insert) with ends, state window, trigger state and flags.
+// win: the 8 columns of fw_session_state (nw each), el: ts, val, ordinal (ne each)
+__global__ __launch_bounds__(256) void k_sr_apply(LCfg c, LState S, int32_t kg, const int64_t* __restrict__ win,
+                                                  const int64_t* __restrict__ eoff, const int64_t* __restrict__ el,
+                                                  int64_t nw, int64_t ne, int64_t base) {
+  long long due = LMAX;
+  unsigned long long ins = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t key = win[i], n = win[7 * nw + i], off = eoff[i];
+    if (n < 0 || off < 0 || off + n > ne) continue;  // (checked by the host)
+    for (int64_t k = 0; k < n; k++) {
+      const int64_t q = base + off + k;
+      S.lpay[q] = LPay{el[off + k], el[ne + off + k], el[2 * ne + off + k], k + 1 < n ? q + 1 : -1};
+      S.lgid[q] = 0;
+    }
+    const int32_t s = sl_insert(S, key, kg, win[nw + i], win[2 * nw + i], sl_home(key) & S.gmask);
+    if (s < 0) continue;  // (LF_MAP_FULL is raised)
+    ins++;
+    const int64_t tstate = win[5 * nw + i], timer = win[6 * nw + i];
+    const uint32_t fl = ((timer & 1) ? GF_TIMER : 0u) | ((timer & 2) ? GF_FPEND : 0u);
+    S.wsst[s] = win[3 * nw + i];
+    S.wsen[s] = win[4 * nw + i];
+    if (c.trigger == FW_TRIGGER_COUNT) S.gtc[s] = tstate;
+    if (S.gfire) S.gfire[s] = tstate;
+    S.g[s].fl = fl;
+    S.g[s].cnt = (int32_t)n;
+    S.whead[s] = n ? base + off : -1;
+    S.wtail[s] = n ? base + off + n - 1 : -1;
+    due = min(due, (long long)sl_timer_of(c, fl, S.wend[s]));
+    if (S.gfire && (fl & GF_FPEND)) due = min(due, (long long)tstate);
+  }
+  block_min(&S.ctr->next_due, due);
+  block_add(&S.ctr->live_groups, ins);
 }
 
 unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256)); }
@@ -1696,6 +1839,9 @@ struct fw_list {
   uint32_t *si = nullptr, *si2 = nullptr;
   int64_t* sprog = nullptr;
   int32_t* pslot = nullptr;
+  unsigned long long* ss_scr = nullptr;  // fw_list_snapshot_sessions' per-slot scratch (4 x ss_cap)
+  int64_t ss_cap = 0;
+  bool poisoned = false;  // a session restore failed after it began to apply: pushes, watermarks and snapshots refuse
 };
 
 namespace {
@@ -1994,6 +2140,12 @@ int sl_alloc_map(fw_list* op, LState& S, int64_t cap) {
   LHIP(op, dmalloc(&S.wend, (size_t)cap));
   LHIP(op, dmalloc(&S.whead, (size_t)cap));
   LHIP(op, dmalloc(&S.wtail, (size_t)cap));
+  S.wsst = S.wsen = S.gtc = nullptr;
+  if (op->cfg.merging_state) {  // (every slot's three values are set where it is claimed: sl_insert)
+    LHIP(op, dmalloc(&S.wsst, (size_t)cap));
+    LHIP(op, dmalloc(&S.wsen, (size_t)cap));
+    LHIP(op, dmalloc(&S.gtc, (size_t)cap));
+  }
   return FW_OK;
 }
 void sl_free_map(LState& S) {
@@ -2001,6 +2153,9 @@ void sl_free_map(LState& S) {
   dfree(S.wend);
   dfree(S.whead);
   dfree(S.wtail);
+  dfree(S.wsst);
+  dfree(S.wsen);
+  dfree(S.gtc);
 }
 // the map rebuilt at gcap slots (tombstones dropped); with `log`, the log compacted first (the live elements in
 // order, their links and the lists' ends remapped)
@@ -2058,15 +2213,13 @@ int sl_check_flags(fw_list* op) {
   if (f & LF_MAP_FULL) return set_err(op, FW_ERR_CAPACITY, "list state map full");
   return FW_OK;
 }
-// processElement for a batch of session-window records (EvictingWindowOperator.java:110-170)
-int sl_push(fw_list* op, const int64_t* key, const int64_t* ts, const int64_t* val, const int32_t* kh, int64_t n) {
-  LRET(read_ctr(op));
-  if (op->c.side_output) LRET(ensure_side(op, (int64_t)op->h_ctr->side + n));
+// room for nw more windows and n more elements (the counters are current): a push's records, a restore's state
+int sl_reserve(fw_list* op, int64_t nw, int64_t n) {
   // the map: every record may open a window; at most 3/4 of the slots live or tombstones during the push
   const int64_t live = (int64_t)op->h_ctr->live_groups, tombs = (int64_t)op->h_ctr->tombs;
-  if (4 * (live + tombs + n) > 3 * op->gcap) {
+  if (4 * (live + tombs + nw) > 3 * op->gcap) {
     int64_t g = op->gcap;
-    while (2 * (live + n) > g) g *= 2;
+    while (2 * (live + nw) > g) g *= 2;
     LRET(sl_compact(op, g, 2 * (int64_t)op->h_ctr->dead > op->n_log));
   }
   // the log: the batch is appended
@@ -2089,6 +2242,13 @@ int sl_push(fw_list* op, const int64_t* key, const int64_t* ts, const int64_t* v
       op->grows++;
     }
   }
+  return FW_OK;
+}
+// processElement for a batch of session-window records (EvictingWindowOperator.java:110-170)
+int sl_push(fw_list* op, const int64_t* key, const int64_t* ts, const int64_t* val, const int32_t* kh, int64_t n) {
+  LRET(read_ctr(op));
+  if (op->c.side_output) LRET(ensure_side(op, (int64_t)op->h_ctr->side + n));
+  LRET(sl_reserve(op, n, n));
   LRET(ensure_rows(op, (int64_t)op->h_ctr->rows + n));  // (at most one firing per element)
   LRET(ensure_sel(op, n));
   LHIP(op, hipMemsetAsync(&op->S.ctr->flags, 0, 8, op->stream));  // flags, need_seq
@@ -2248,6 +2408,26 @@ int push_device(fw_list* op, const int64_t* key, const int64_t* ts, const int64_
   return maybe_compact(op);
 }
 
+// the key group of a Long / Integer key: MathUtils.murmurHash of its hashCode (host restatement) % maxParallelism
+int32_t host_key_group(const LCfg& cfg, int64_t k) {
+  const int32_t h = cfg.key_kind == FW_KEY_INT ? (int32_t)k : (int32_t)(k ^ (int64_t)((uint64_t)k >> 32));
+  uint32_t c = (uint32_t)h;
+  c *= 0xcc9e2d51u;
+  c = (c << 15) | (c >> 17);
+  c *= 0x1b873593u;
+  c = (c << 13) | (c >> 19);
+  c = c * 5u + 0xe6546b64u;
+  c ^= 4u;
+  c ^= c >> 16;
+  c *= 0x85ebca6bu;
+  c ^= c >> 13;
+  c *= 0xc2b2ae35u;
+  c ^= c >> 16;
+  int32_t r = (int32_t)c;
+  r = r >= 0 ? r : (r != INT32_MIN ? -r : 0);
+  return r % cfg.max_par;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2267,9 +2447,13 @@ int fw_list_create(const fw_list_config* cfg, fw_list** out) {
     return fail(FW_ERR_UNSUPPORTED, "assigner must be FW_TUMBLING, FW_SLIDING, FW_SESSION or FW_GLOBAL");
   if (c.assigner == FW_SESSION && c.size <= 0)
     return fail(FW_ERR_ARG, "EventTimeSessionWindows parameters must satisfy 0 < size");
-  if (c.assigner == FW_SESSION && c.trigger != FW_TRIGGER_EVENT_TIME && c.trigger != FW_TRIGGER_CONTINUOUS_EVENT_TIME)
+  if (c.merging_state != 0 && (c.merging_state != 1 || c.assigner != FW_SESSION))
+    return fail(FW_ERR_ARG, "merging_state is 0 or 1, and 1 only with FW_SESSION");
+  if (c.assigner == FW_SESSION && !c.merging_state && c.trigger != FW_TRIGGER_EVENT_TIME &&
+      c.trigger != FW_TRIGGER_CONTINUOUS_EVENT_TIME)
     return fail(FW_ERR_UNSUPPORTED, "session windows over ListState are offered with EventTimeTrigger or "
-                                    "ContinuousEventTimeTrigger (or PurgingTrigger of either)");
+                                    "ContinuousEventTimeTrigger (or PurgingTrigger of either); CountTrigger needs "
+                                    "merging_state = 1");
   if (c.assigner == FW_TUMBLING && (c.size <= 0 || c.offset < 0 || c.offset >= c.size))
     return fail(FW_ERR_ARG, "TumblingEventTimeWindows parameters must satisfy 0 <= offset < size");
   if (c.assigner == FW_SLIDING && (c.size <= 0 || c.slide <= 0 || c.slide > c.size || c.offset < 0 || c.offset >= c.slide))
@@ -2356,6 +2540,7 @@ void fw_list_destroy(fw_list* op) {
   dfree(op->si2);
   dfree(op->sprog);
   dfree(op->pslot);
+  dfree(op->ss_scr);
   for (int64_t** p : {&op->S.rkey, &op->S.rstart, &op->S.rend, &op->S.rcnt, &op->S.rsum, &op->S.rmin, &op->S.rmax,
                       &op->S.rfirst, &op->S.roff, &op->S.ets, &op->S.eval, &op->S.eord, &op->S.skey, &op->S.sts,
                       &op->S.sval, &op->in_key, &op->in_ts, &op->in_val})
@@ -2387,6 +2572,7 @@ int fw_list_push_batch_device(fw_list* op, const int64_t* key, const int64_t* ts
                               const int32_t* key_hash, int64_t n) {
   if (!op || n < 0 || (n && (!key || !ts || !val))) return set_err(op, FW_ERR_ARG, "invalid arguments");
   (void)hipSetDevice(op->device);
+  if (op->poisoned) return set_err(op, FW_ERR_STATE, "the handle is unusable: a session restore failed half-way");
   return push_device(op, key, ts, (const int64_t*)val, key_hash, n);
 }
 
@@ -2394,6 +2580,7 @@ int fw_list_push_batch(fw_list* op, const int64_t* key, const int64_t* ts, const
                        int64_t n) {
   if (!op || n < 0 || (n && (!key || !ts || !val))) return set_err(op, FW_ERR_ARG, "invalid arguments");
   (void)hipSetDevice(op->device);
+  if (op->poisoned) return set_err(op, FW_ERR_STATE, "the handle is unusable: a session restore failed half-way");
   for (int64_t i = 0; i < n; i++)  // host columns: refused before anything is copied or counted
     if (ts[i] != LMIN && runaway(op->c, ts[i])) return runaway_error(op);
   for (int64_t o = 0; o < n; o += op->max_batch) {
@@ -2411,6 +2598,7 @@ int fw_list_push_batch(fw_list* op, const int64_t* key, const int64_t* ts, const
 int fw_list_advance_watermark(fw_list* op, int64_t wm, int64_t* n_pending_rows) {
   if (!op) return FW_ERR_ARG;
   (void)hipSetDevice(op->device);
+  if (op->poisoned) return set_err(op, FW_ERR_STATE, "the handle is unusable: a session restore failed half-way");
   LRET(read_ctr(op));
   if (wm > op->wm && wm < op->h_ctr->next_due) {
     op->wm = wm;  // no timer is due
@@ -2552,7 +2740,9 @@ int fw_list_snapshot_key_group(fw_list* op, int32_t key_group, const fw_list_sta
                                int64_t cap_elems, int64_t* n_lists, int64_t* n_elems) {
   if (!op) return FW_ERR_ARG;
   (void)hipSetDevice(op->device);
-  if (sessions(op)) return set_err(op, FW_ERR_UNSUPPORTED, "session windows' list state is not offered for snapshots");
+  if (sessions(op))
+    return set_err(op, FW_ERR_UNSUPPORTED, "session windows' list state is not offered for snapshots in fw_list_state "
+                                           "(merging_state = 1 and fw_list_snapshot_sessions carry it)");
   if ((uint32_t)(key_group - op->c.kg0) >= (uint32_t)op->c.nkg)
     return set_err(op, FW_ERR_KEY_GROUP, "key group %d is not in the handle's KeyGroupRange", key_group);
   // the key group's lists: its live groups, and its live elements grouped by list in list order
@@ -2625,7 +2815,9 @@ int fw_list_restore_key_group(fw_list* op, int32_t key_group, const fw_list_stat
                               int64_t n_elems) {
   if (!op || (n_lists && !src)) return set_err(op, FW_ERR_ARG, "invalid arguments");
   (void)hipSetDevice(op->device);
-  if (sessions(op)) return set_err(op, FW_ERR_UNSUPPORTED, "session windows' list state is not offered for snapshots");
+  if (sessions(op))
+    return set_err(op, FW_ERR_UNSUPPORTED, "session windows' list state is not offered for snapshots in fw_list_state "
+                                           "(merging_state = 1 and fw_list_restore_sessions carry it)");
   if ((uint32_t)(key_group - op->c.kg0) >= (uint32_t)op->c.nkg)
     return set_err(op, FW_ERR_KEY_GROUP, "key group %d is not in the handle's KeyGroupRange", key_group);
   if (n_lists == 0) return FW_OK;
@@ -2640,23 +2832,7 @@ int fw_list_restore_key_group(fw_list* op, int32_t key_group, const fw_list_stat
                      (long long)s, (long long)src->end[i]);
     if (op->c.key_kind != FW_KEY_HASHED) {
       const int64_t k = src->key[i];
-      const int32_t h = op->c.key_kind == FW_KEY_INT ? (int32_t)k : (int32_t)(k ^ (int64_t)((uint64_t)k >> 32));
-      // MathUtils.murmurHash (host restatement) % maxParallelism
-      uint32_t c = (uint32_t)h;
-      c *= 0xcc9e2d51u;
-      c = (c << 15) | (c >> 17);
-      c *= 0x1b873593u;
-      c = (c << 13) | (c >> 19);
-      c = c * 5u + 0xe6546b64u;
-      c ^= 4u;
-      c ^= c >> 16;
-      c *= 0x85ebca6bu;
-      c ^= c >> 13;
-      c *= 0xc2b2ae35u;
-      c ^= c >> 16;
-      int32_t r = (int32_t)c;
-      r = r >= 0 ? r : (r != INT32_MIN ? -r : 0);
-      if (r % op->c.max_par != key_group)
+      if (host_key_group(op->c, k) != key_group)
         return set_err(op, FW_ERR_KEY_GROUP, "key %lld is not in key group %d", (long long)k, key_group);
     }
   }
@@ -2709,5 +2885,185 @@ int fw_list_restore_key_group(fw_list* op, int32_t key_group, const fw_list_stat
   op->ord_base = std::max(op->ord_base, max_ord + 1);
   return FW_OK;
 }
+
+// (both session entry points free their staging through a local `done`)
+#define SHIP(expr)                                                                                        \
+  do {                                                                                                    \
+    hipError_t _e = (expr);                                                                               \
+    if (_e != hipSuccess) return done(set_err(op, FW_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e))); \
+  } while (0)
+
+// The MergingWindowSet form of a key group's session state, gathered on the device: a flag-and-length pass over the
+// map slots, two scans, one thread per window writing its columns and walking its list into its offset, then
+// contiguous copies to the host.
+int fw_list_snapshot_sessions(fw_list* op, int32_t key_group, const fw_session_state* dst, int64_t cap_windows,
+                              int64_t cap_elems, int64_t* n_windows, int64_t* n_elems) {
+  if (!op) return FW_ERR_ARG;
+  (void)hipSetDevice(op->device);
+  if (op->poisoned) return set_err(op, FW_ERR_STATE, "the handle is unusable: a session restore failed half-way");
+  if (!op->cfg.merging_state)
+    return set_err(op, FW_ERR_UNSUPPORTED, "session snapshots need a handle created with merging_state = 1");
+  if ((uint32_t)(key_group - op->c.kg0) >= (uint32_t)op->c.nkg)
+    return set_err(op, FW_ERR_KEY_GROUP, "key group %d is not in the handle's KeyGroupRange", key_group);
+  const size_t cap = (size_t)op->gcap;
+  int64_t *win = nullptr, *el = nullptr;
+  auto done = [&](int rc) {
+    dfree(win);
+    dfree(el);
+    return rc;
+  };
+  // per-slot scratch kept on the handle (a checkpoint snapshots every key group in turn): flags, lengths, their scans
+  if (op->ss_cap < op->gcap) {
+    dfree(op->ss_scr);
+    op->ss_cap = 0;
+    SHIP(dmalloc(&op->ss_scr, 4 * cap));
+    op->ss_cap = op->gcap;
+  }
+  unsigned long long *wf = op->ss_scr, *wl = wf + cap, *wfs = wl + cap, *wls = wfs + cap;
+  hipLaunchKernelGGL(k_ss_flags, dim3(grid_for(op->gcap)), dim3(256), 0, op->stream, op->S, key_group, wf, wl);
+  SHIP(hipGetLastError());
+  const unsigned long long* in[] = {wf, wl};
+  unsigned long long* out[] = {wfs, wls};
+  for (int i = 0; i < 2; i++) {
+    size_t bytes = 0;
+    SHIP(rocprim::inclusive_scan(nullptr, bytes, in[i], out[i], cap, rocprim::plus<unsigned long long>(), op->stream));
+    if (ensure_tmp(op, bytes) != FW_OK) return done(FW_ERR_HIP);
+    bytes = op->tmp_bytes;
+    SHIP(rocprim::inclusive_scan(op->tmp, bytes, in[i], out[i], cap, rocprim::plus<unsigned long long>(), op->stream));
+  }
+  unsigned long long tot[2] = {0, 0};
+  SHIP(hipMemcpyAsync(&tot[0], wfs + cap - 1, 8, hipMemcpyDeviceToHost, op->stream));
+  SHIP(hipMemcpyAsync(&tot[1], wls + cap - 1, 8, hipMemcpyDeviceToHost, op->stream));
+  SHIP(hipStreamSynchronize(op->stream));
+  const int64_t nw = (int64_t)tot[0], ne = (int64_t)tot[1];
+  if (n_windows) *n_windows = nw;
+  if (n_elems) *n_elems = ne;
+  if (!dst || nw > cap_windows || ne > cap_elems || nw == 0) return done(FW_OK);
+  SHIP(dmalloc(&win, (size_t)nw * 8));
+  SHIP(dmalloc(&el, (size_t)ne * 3));
+  if (ne) SHIP(hipMemsetAsync(el, 0, (size_t)ne * 24, op->stream));  // (a list shorter than its cnt leaves zeros)
+  hipLaunchKernelGGL(k_ss_write, dim3(grid_for(op->gcap)), dim3(256), 0, op->stream, op->c, op->S, key_group, wfs, wls,
+                     nw, ne, win, el);
+  SHIP(hipGetLastError());
+  int64_t* wd[] = {dst->key, dst->start, dst->end, dst->state_start, dst->state_end, dst->trigger_state, dst->timer,
+                   dst->n_elems};
+  int64_t* ed[] = {dst->ts, dst->val, dst->ordinal};
+  for (int i = 0; i < 8; i++)
+    if (wd[i]) SHIP(hipMemcpyAsync(wd[i], win + (size_t)i * nw, (size_t)nw * 8, hipMemcpyDeviceToHost, op->stream));
+  for (int i = 0; i < 3; i++)
+    if (ed[i] && ne) SHIP(hipMemcpyAsync(ed[i], el + (size_t)i * ne, (size_t)ne * 8, hipMemcpyDeviceToHost, op->stream));
+  SHIP(hipStreamSynchronize(op->stream));
+  return done(FW_OK);
+}
+
+int fw_list_restore_sessions(fw_list* op, int32_t key_group, const fw_session_state* src, int64_t n_windows,
+                             int64_t n_elems) {
+  if (!op || n_windows < 0 || n_elems < 0 || (n_windows && !src)) return set_err(op, FW_ERR_ARG, "invalid arguments");
+  (void)hipSetDevice(op->device);
+  if (op->poisoned) return set_err(op, FW_ERR_STATE, "the handle is unusable: a session restore failed half-way");
+  if (!op->cfg.merging_state)
+    return set_err(op, FW_ERR_UNSUPPORTED, "session snapshots need a handle created with merging_state = 1");
+  if ((uint32_t)(key_group - op->c.kg0) >= (uint32_t)op->c.nkg)
+    return set_err(op, FW_ERR_KEY_GROUP, "key group %d is not in the handle's KeyGroupRange", key_group);
+  if (n_windows == 0) return n_elems ? set_err(op, FW_ERR_ARG, "list lengths do not add up to n_elems") : FW_OK;
+  if (!src->key || !src->start || !src->end || !src->state_start || !src->state_end || !src->trigger_state ||
+      !src->timer || !src->n_elems || (n_elems && (!src->ts || !src->val || !src->ordinal)))
+    return set_err(op, FW_ERR_ARG, "a column of the session state is missing");
+  // the columns, checked on the host before anything changes
+  const int64_t nw = n_windows;
+  std::vector<int64_t> eoff((size_t)nw);
+  int64_t total = 0, max_ord = -1;
+  for (int64_t i = 0; i < nw; i++) {
+    const int64_t n = src->n_elems[i];
+    if (n < 0 || n > INT32_MAX || total + n > n_elems) return set_err(op, FW_ERR_ARG, "list lengths do not add up to n_elems");
+    eoff[(size_t)i] = total;
+    total += n;
+    if ((int64_t)((uint64_t)src->end[i] - (uint64_t)src->start[i]) < op->c.size)
+      return set_err(op, FW_ERR_ARG, "window %lld: [%lld, %lld) is shorter than the session gap", (long long)i,
+                     (long long)src->start[i], (long long)src->end[i]);
+    if (src->timer[i] & ~(int64_t)(op->S.gfire ? 3 : op->c.trigger == FW_TRIGGER_COUNT ? 0 : 1))
+      return set_err(op, FW_ERR_ARG, "window %lld: timer bits %lld are not this trigger's", (long long)i,
+                     (long long)src->timer[i]);
+    if (op->c.trigger == FW_TRIGGER_COUNT && (src->trigger_state[i] < 0 || src->trigger_state[i] >= op->c.trig_n))
+      return set_err(op, FW_ERR_ARG, "window %lld: CountTrigger count outside [0, n)", (long long)i);
+    if (op->c.key_kind != FW_KEY_HASHED && host_key_group(op->c, src->key[i]) != key_group)
+      return set_err(op, FW_ERR_KEY_GROUP, "key %lld is not in key group %d", (long long)src->key[i], key_group);
+  }
+  if (total != n_elems) return set_err(op, FW_ERR_ARG, "list lengths do not add up to n_elems");
+  for (int64_t i = 0; i < n_elems; i++) max_ord = std::max(max_ord, src->ordinal[i]);
+  {  // per key: the windows pairwise non-intersecting (TimeWindow.intersects), the state windows distinct
+    std::vector<int64_t> ix((size_t)nw);
+    for (int64_t i = 0; i < nw; i++) ix[(size_t)i] = i;
+    std::sort(ix.begin(), ix.end(), [&](int64_t a, int64_t b) {
+      return src->key[a] != src->key[b] ? src->key[a] < src->key[b] : src->start[a] < src->start[b];
+    });
+    for (int64_t j = 1; j < nw; j++) {
+      const int64_t a = ix[(size_t)j - 1], b = ix[(size_t)j];
+      // (ascending starts within a key, every earlier end below the next start: it is enough to look at neighbours)
+      if (src->key[a] == src->key[b] && src->start[b] <= src->end[a])
+        return set_err(op, FW_ERR_ARG, "key %lld: windows [%lld, %lld) and [%lld, %lld) intersect", (long long)src->key[a],
+                       (long long)src->start[a], (long long)src->end[a], (long long)src->start[b], (long long)src->end[b]);
+    }
+    std::sort(ix.begin(), ix.end(), [&](int64_t a, int64_t b) {
+      if (src->key[a] != src->key[b]) return src->key[a] < src->key[b];
+      if (src->state_start[a] != src->state_start[b]) return src->state_start[a] < src->state_start[b];
+      return src->state_end[a] < src->state_end[b];
+    });
+    for (int64_t j = 1; j < nw; j++) {
+      const int64_t a = ix[(size_t)j - 1], b = ix[(size_t)j];
+      if (src->key[a] == src->key[b] && src->state_start[a] == src->state_start[b] && src->state_end[a] == src->state_end[b])
+        return set_err(op, FW_ERR_ARG, "key %lld: two windows share the state window [%lld, %lld)", (long long)src->key[a],
+                       (long long)src->state_start[a], (long long)src->state_end[a]);
+    }
+  }
+  // staged on the device: the 8 window columns, the element offsets, the 3 element columns
+  int64_t *win = nullptr, *off = nullptr, *el = nullptr;
+  unsigned int* found = nullptr;
+  auto done = [&](int rc) {
+    dfree(win);
+    dfree(off);
+    dfree(el);
+    dfree(found);
+    return rc;
+  };
+  SHIP(dmalloc(&win, (size_t)nw * 8));
+  SHIP(dmalloc(&off, (size_t)nw));
+  SHIP(dmalloc(&el, (size_t)n_elems * 3));
+  SHIP(dmalloc(&found, 1));
+  const int64_t* ws[] = {src->key, src->start, src->end, src->state_start, src->state_end, src->trigger_state,
+                         src->timer, src->n_elems};
+  const int64_t* es[] = {src->ts, src->val, src->ordinal};
+  for (int i = 0; i < 8; i++)
+    SHIP(hipMemcpyAsync(win + (size_t)i * nw, ws[i], (size_t)nw * 8, hipMemcpyHostToDevice, op->stream));
+  for (int i = 0; i < 3 && n_elems; i++)
+    SHIP(hipMemcpyAsync(el + (size_t)i * n_elems, es[i], (size_t)n_elems * 8, hipMemcpyHostToDevice, op->stream));
+  SHIP(hipMemcpyAsync(off, eoff.data(), (size_t)nw * 8, hipMemcpyHostToDevice, op->stream));
+  SHIP(hipMemsetAsync(found, 0, 4, op->stream));
+  // no key of the snapshot may have an in-flight window in the handle: nothing has changed when this refuses
+  hipLaunchKernelGGL(k_sr_check, dim3(grid_for(nw)), dim3(256), 0, op->stream, op->S, win, nw, found);
+  SHIP(hipGetLastError());
+  unsigned int hfound = 0;
+  SHIP(hipMemcpyAsync(&hfound, found, 4, hipMemcpyDeviceToHost, op->stream));
+  SHIP(hipStreamSynchronize(op->stream));  // (the host columns are staged)
+  if (hfound) return done(set_err(op, FW_ERR_STATE, "a key of the snapshot already has an in-flight window in the handle"));
+  int rc = read_ctr(op);
+  if (rc == FW_OK) rc = sl_reserve(op, nw, n_elems);
+  if (rc != FW_OK) return done(rc);
+  SHIP(hipMemsetAsync(&op->S.ctr->flags, 0, 4, op->stream));
+  hipLaunchKernelGGL(k_sr_apply, dim3(grid_for(nw)), dim3(256), 0, op->stream, op->c, op->S, key_group, win, off, el, nw,
+                     n_elems, op->n_log);
+  SHIP(hipGetLastError());
+  rc = read_ctr(op);
+  // (sl_reserve left room for every window, so the map cannot fill; if it did, or the device failed, the handle is
+  // partly restored: it refuses everything from here on)
+  if (rc != FW_OK || (op->h_ctr->flags & LF_MAP_FULL)) {
+    op->poisoned = true;
+    return done(set_err(op, FW_ERR_STATE, "session restore failed half-way; the handle is unusable"));
+  }
+  op->n_log += n_elems;
+  op->ord_base = std::max(op->ord_base, max_ord + 1);
+  return done(FW_OK);
+}
+#undef SHIP
 
 }  // extern "C"

@@ -172,6 +172,27 @@ class TimeWindowSer:
         w.i64(v[1])
 
 
+VOID_NAMESPACE = "VoidNamespace"  # the one instance (VoidNamespace.INSTANCE), as a value of this module
+
+
+class VoidNamespaceSer:
+    """VoidNamespaceSerializer (flink-runtime/.../state/VoidNamespaceSerializer.java): one byte 0 — the namespace of
+    state that is not scoped to a window, such as the WindowOperator's "merging-window-set" """
+
+    def read(self, r):
+        if r.u8() != 0:
+            raise ValueError("corrupt VoidNamespace")
+        return VOID_NAMESPACE
+
+    def write(self, w, v):
+        w.u8(0)
+
+
+def void_namespace_hash(_=None):
+    """VoidNamespace.hashCode (VoidNamespace.java): the constant 99"""
+    return 99
+
+
 class TupleSer:
     """TupleSerializer: the fields in order, no null mask"""
 
@@ -710,26 +731,42 @@ def write_timer_section(services, key_ser, ns_ser, versioned=True):
     return w.getvalue()
 
 
-def write_savepoint_key_group_0(meta, timer_meta, mappings, event_timers, serializers, chain_index, managed_name,
-                                raw_name, table="copy_on_write", key_hash=None, ns_hash=None):
+def write_savepoint_key_group_0_states(meta, timer_meta, mappings, event_timers, serializers, chain_index,
+                                       managed_name, raw_name, table="copy_on_write", key_hash=None, ns_hashes=None,
+                                       timer_state="window-contents", timer_ns_hash=None):
     """A WindowOperator's savepoint file for a one-key-group range (the test harness' maxParallelism 1: key group 0)
-    from its content: `mappings` [(window, key, state)] of the one registered state and the `event_timers` of
-    "window-timers" (any order: written in the heap's iteration order, `table` as in heap_section_order), with the
-    host's serializer blocks and handle names (meta / timer_meta as read_heap_keyed_state / read_timers return
-    them).  String keys and TimeWindow namespaces unless key_hash / ns_hash say otherwise."""
+    with several registered states: `mappings` {state name: [(namespace, key, state)]} for the states of
+    meta["states"], which are written in that order (the host's registration order) under their index as the state id
+    (HeapKeyedStateBackend.java:366-383); a state without mappings is written with count 0.  Every state's mappings
+    and the `event_timers` of "window-timers" may come in any order: they are written in the heap's iteration order
+    (`table` as in heap_section_order).  ns_hashes {state name: namespace hash}: TimeWindow namespaces unless given
+    (void_namespace_hash for "merging-window-set").  The timers' key and namespace serializers are `timer_state`'s."""
     from .keygroups import string_hash_code
     key_hash = key_hash or string_hash_code
-    ns_hash = ns_hash or time_window_hash
-    (typ, name), = meta["states"]
+    ns_hashes = ns_hashes or {}
     hdr = write_serialization_proxy(meta["version"], meta["serializers"]["key"],
-                                    [(typ, name, meta["serializers"][name])])
-    sec = write_key_group_section(0, [(0, name, heap_section_order(mappings, key_hash, ns_hash, table))], serializers)
+                                    [(typ, name, meta["serializers"][name]) for typ, name in meta["states"]])
+    sec = write_key_group_section(
+        0, [(sid, name, heap_section_order(mappings.get(name, []), key_hash, ns_hashes.get(name, time_window_hash),
+                                           table)) for sid, (_, name) in enumerate(meta["states"])], serializers)
     stream, offsets = write_keyed_state_stream(hdr, [sec])
     timers = write_timer_section([("window-timers", timer_meta["serializers"]["window-timers"],
-                                   timer_set_order(event_timers, key_hash, ns_hash), [])],
-                                 serializers[name][1], serializers[name][0], versioned=timer_meta["versioned"])
+                                   timer_set_order(event_timers, key_hash, timer_ns_hash or time_window_hash), [])],
+                                 serializers[timer_state][1], serializers[timer_state][0],
+                                 versioned=timer_meta["versioned"])
     return write_operator_snapshot(chain_index, [write_keyed_handle(0, [0], raw_name, timers)],
                                    [write_keyed_handle(0, offsets, managed_name, stream)])
+
+
+def write_savepoint_key_group_0(meta, timer_meta, mappings, event_timers, serializers, chain_index, managed_name,
+                                raw_name, table="copy_on_write", key_hash=None, ns_hash=None):
+    """write_savepoint_key_group_0_states for an operator with one registered state: `mappings` [(window, key,
+    state)] of that state.  String keys and TimeWindow namespaces unless key_hash / ns_hash say otherwise."""
+    (_, name), = meta["states"]
+    return write_savepoint_key_group_0_states(meta, timer_meta, {name: mappings}, event_timers, serializers,
+                                              chain_index, managed_name, raw_name, table=table, key_hash=key_hash,
+                                              ns_hashes={name: ns_hash} if ns_hash else None, timer_state=name,
+                                              timer_ns_hash=ns_hash)
 
 
 def rows_to_timers(rows, key_name, service_timer=lambda r: int(r["end"]) - 1):
@@ -817,3 +854,106 @@ def heap_from_list_state(lists, elems, key_name, make_value):
                     [make_value(elems[k + j]) for j in range(n)]))
         k += n
     return out
+
+
+# ---------------------------------------------------------------- session windows: MergingWindowSet form
+def session_state_from_heap(contents, mapping, timers, key_id, value_of, ts_of=None, ordinal_base=0, counts=None,
+                            fire_times=None):
+    """A merging WindowOperator's keyed state as the list operator's session state (fw_session_state): (windows
+    [dict key, start, end, state_start, state_end, trigger_state, timer, n_elems], elements [(ts, val, ordinal)]).
+    contents: "window-contents" [(state window, key, values)]; mapping: "merging-window-set" [(VoidNamespace, key,
+    [(actual window, state window)])]; counts: CountTrigger's {(key, actual window): count}
+    (trigger_counts_from_heap) or fire_times: ContinuousEventTimeTrigger's (fire_times_from_heap) -- the trigger's
+    state is kept under the actual window, the list under the state window, and a purged window exists in the mapping
+    only.  timer bit 1: the window's maxTimestamp timer is among `timers` and is not its cleanup timer's only reason
+    (under CountTrigger no trigger timer exists: the bit stays 0); bit 2: the timer at the fire time is."""
+    lists = {(key, tuple(sw)): values for sw, key, values in contents}
+    wins, elems = [], []
+    o = ordinal_base
+    for _, key, pairs in mapping:
+        for actual, state in pairs:
+            actual, state = tuple(actual), tuple(state)
+            values = lists.get((key, state), [])
+            ts_state, timer = 0, 0
+            if counts is not None:
+                ts_state = counts.get((key, actual), 0)
+            elif fire_times is not None:
+                ts_state = fire_times.get((key, actual), -(1 << 63))
+                timer = int((key, actual, actual[1] - 1) in timers) | 2 * int((key, actual, ts_state) in timers)
+            else:
+                timer = int((key, actual, actual[1] - 1) in timers)
+            wins.append(dict(key=key_id(key), start=actual[0], end=actual[1], state_start=state[0],
+                             state_end=state[1], trigger_state=ts_state, timer=timer, n_elems=len(values)))
+            for v in values:
+                ts = ts_of(v) if ts_of else None
+                elems.append((-(1 << 63) if ts is None else ts, value_of(v), o))
+                o += 1
+    return wins, elems
+
+
+def heap_from_session_state(wins, elems, key_name, make_value, lateness=0, count_trigger=False):
+    """The list operator's session state back to the heap's content: {"window-contents": [(state window, key,
+    values)] of the non-empty lists, "merging-window-set": [(VoidNamespace, key, [(actual, state)])] one entry per
+    key, "count": [(actual window, key, count)] of the non-zero counts (count_trigger)}, and the event-time timers:
+    every window's cleanup timer (maxTimestamp + lateness) plus its maxTimestamp timer when registered (timer bit 1).
+    make_value(key name, element) builds a list's value.
+    ContinuousEventTimeTrigger's fire-time timers stay out: the stale timers of merged windows are not kept on the
+    GPU, so that trigger's timer set cannot be rebuilt.  Several pairs of one key are written in hash_set_order of the
+    actual windows inserted by ascending start; the reference's fixtures hold one window per key, so this order is
+    unpinned."""
+    contents, counts, timers, per_key, order = [], [], set(), {}, []
+    k = 0
+    for r in wins:
+        n = int(r["n_elems"])
+        key = key_name(int(r["key"]))
+        actual, state = (int(r["start"]), int(r["end"])), (int(r["state_start"]), int(r["state_end"]))
+        if n:
+            contents.append((state, key, [make_value(key, elems[k + j]) for j in range(n)]))
+        k += n
+        if count_trigger and int(r["trigger_state"]):
+            counts.append((actual, key, int(r["trigger_state"])))
+        timers.add((key, actual, actual[1] - 1 + lateness))
+        if int(r["timer"]) & 1:
+            timers.add((key, actual, actual[1] - 1))
+        if key not in per_key:
+            order.append(key)
+        per_key.setdefault(key, []).append((actual, state))
+    mapping = []
+    for key in order:
+        pairs = dict(per_key[key])
+        mapping.append((VOID_NAMESPACE, key, [(a, pairs[a]) for a in hash_set_order(sorted(pairs), time_window_hash)]))
+    out = {"window-contents": contents, "merging-window-set": mapping}
+    if count_trigger:
+        out["count"] = counts
+    return out, timers
+
+
+def session_rows_from_heap(mappings, mapping, timers, key_id, row_of):
+    """An aggregating session operator's state (fw_op with FW_SESSION: one accumulator per window) from the heap:
+    mappings [(state window, key, accumulator)] keyed by the state window, resolved through "merging-window-set" to
+    the actual window the GPU rows are keyed by.  row_of(accumulator) -> dict of the row's count / sum / min / max."""
+    acc = {(key, tuple(sw)): a for sw, key, a in mappings}
+    rows = []
+    for _, key, pairs in mapping:
+        for actual, state in pairs:
+            a = acc.get((key, tuple(state)))
+            if a is None:
+                continue
+            rows.append(dict(key=key_id(key), start=actual[0], end=actual[1],
+                             timer=int((key, tuple(actual), actual[1] - 1) in timers), **row_of(a)))
+    return rows
+
+
+def heap_from_session_rows(rows, key_name, make_accumulator):
+    """GPU session rows (keyed by the actual window) to the heap's content: the accumulators under the actual window
+    and the identity mapping actual -> actual, one "merging-window-set" entry per key."""
+    contents, per_key, order = [], {}, []
+    for r in rows:
+        key, w = key_name(int(r["key"])), (int(r["start"]), int(r["end"]))
+        contents.append((w, key, make_accumulator(r)))
+        if key not in per_key:
+            order.append(key)
+        per_key.setdefault(key, []).append(w)
+    mapping = [(VOID_NAMESPACE, key, [(w, w) for w in hash_set_order(sorted(per_key[key]), time_window_hash)])
+               for key in order]
+    return {"window-contents": contents, "merging-window-set": mapping}

@@ -6,8 +6,13 @@ with an Iterable window function, and the EvictingWindowOperator (f4; include/fl
   EvictingWindowOperator(..., trigger, evictor, ...)            (EvictingWindowOperator.java:76-98)
   processElement -> process_batch, processWatermark -> process_watermark   (EvictingWindowOperator.java:102-286)
 
-Triggers: EventTimeTrigger, CountTrigger.of(n) (not over sessions), ContinuousEventTimeTrigger.of(interval) — early
-firings, possibly several of one window per watermark — each alone or inside PurgingTrigger.
+Triggers: EventTimeTrigger, CountTrigger.of(n), ContinuousEventTimeTrigger.of(interval) — early firings, possibly
+several of one window per watermark — each alone or inside PurgingTrigger.
+
+Session windows keep, by default, only what firing needs.  `merging_state=True` (EventTimeSessionWindows only) makes the
+handle keep the full MergingWindowSet form per in-flight window — its state window and the trigger's count — and with
+it come CountTrigger over sessions and keyed-state snapshots (snapshot_sessions_key_group / restore_sessions_key_group,
+SESSION_STATE_DTYPE; snapshot_state / initialize_state use them).  Without the flag a session handle refuses both.
 
 Every firing yields a row (key, window, count, the built-in reduce sum / min / max over the contents, the first
 element's arrival ordinal) and, with emit_contents, its elements in list order, on which `window_function(key,
@@ -27,13 +32,16 @@ from .windowing import (VALUE_TYPES, ContinuousEventTimeTrigger, CountTrigger, E
 LIST_ROW_FIELDS = ("key", "start", "end", "count", "sum", "min", "max", "first", "elem_off")
 LIST_ROW_DTYPE = np.dtype([(f, "<i8") for f in LIST_ROW_FIELDS] + [("epoch", "<i8")])
 SIDE_DTYPE = np.dtype([("key", "<i8"), ("ts", "<i8"), ("val", "<i8"), ("epoch", "<i8")])
+# one in-flight session window (fw_session_state): the window, its state window, the trigger's state, timer bits, length
+SESSION_STATE_DTYPE = np.dtype([(f, "<i8") for f in ("key", "start", "end", "state_start", "state_end", "trigger_state",
+                                                    "timer", "n_elems")])
 
 
 class GpuListWindowOperator:
     def __init__(self, assigner: WindowAssigner, trigger: Trigger = None, evictor: Evictor = None,
                  allowed_lateness=0, side_output=False, value_type="long", key_type="long", max_parallelism=128,
                  key_group_range: KeyGroupRange = None, emit_contents=True, window_function=None, device=0,
-                 expected_elements=0, max_batch=0):
+                 expected_elements=0, max_batch=0, merging_state=False):
         trigger = trigger or EventTimeTrigger.create()
         nested = getattr(trigger, "nested", trigger)
         if not isinstance(nested, (EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger)):
@@ -66,6 +74,8 @@ class GpuListWindowOperator:
         c.device = device
         c.allowed_lateness = allowed_lateness
         c.expected_elements, c.max_batch = expected_elements, max_batch
+        c.merging_state = int(bool(merging_state))
+        self.merging_state = bool(merging_state)
         self.assigner, self.trigger, self.evictor = assigner, trigger, evictor
         self.value_type, self.key_group_range = value_type, kgr
         self.emit_contents, self.window_function = bool(emit_contents), window_function
@@ -251,7 +261,37 @@ class GpuListWindowOperator:
             el[f] = ec[f]
         return lists, el
 
+    def snapshot_sessions_key_group(self, kg):
+        """(windows SESSION_STATE_DTYPE, elements ELEM_DTYPE concatenated in list order) of key group kg of a
+        merging_state handle: every in-flight window with its state window, the trigger's state (CountTrigger's count,
+        ContinuousEventTimeTrigger's fire time, else 0) and the timer bits of snapshot_key_group."""
+        L = N.lib()
+        nw, ne = ctypes.c_int64(), ctypes.c_int64()
+        self._check(L.fw_list_snapshot_sessions(self._h, int(kg), None, 0, 0, ctypes.byref(nw), ctypes.byref(ne)))
+        wc = {f: np.zeros(nw.value, dtype=np.int64) for f in SESSION_STATE_DTYPE.names}
+        ec = {f: np.zeros(ne.value, dtype=np.int64) for f in ELEM_DTYPE.names}
+        st = N.FwSessionState(**{f: wc[f].ctypes.data for f in wc}, **{f: ec[f].ctypes.data for f in ec})
+        self._check(L.fw_list_snapshot_sessions(self._h, int(kg), ctypes.byref(st), nw.value, ne.value,
+                                                ctypes.byref(nw), ctypes.byref(ne)))
+        wins = np.zeros(nw.value, dtype=SESSION_STATE_DTYPE)
+        for f in wc:
+            wins[f] = wc[f]
+        el = np.zeros(ne.value, dtype=ELEM_DTYPE)
+        for f in ec:
+            el[f] = ec[f]
+        return wins, el
+
+    def restore_sessions_key_group(self, kg, windows, elems):
+        windows = np.ascontiguousarray(windows, dtype=SESSION_STATE_DTYPE)
+        elems = np.ascontiguousarray(elems, dtype=ELEM_DTYPE)
+        wc = {f: np.ascontiguousarray(windows[f]) for f in SESSION_STATE_DTYPE.names}
+        ec = {f: np.ascontiguousarray(elems[f]) for f in ELEM_DTYPE.names}
+        st = N.FwSessionState(**{f: wc[f].ctypes.data for f in wc}, **{f: ec[f].ctypes.data for f in ec})
+        self._check(N.lib().fw_list_restore_sessions(self._h, int(kg), ctypes.byref(st), len(windows), len(elems)))
+
     def snapshot_state(self):
+        if self.merging_state:
+            return {kg: self.snapshot_sessions_key_group(kg) for kg in self.key_group_range}
         return {kg: self.snapshot_key_group(kg) for kg in self.key_group_range}
 
     def restore_key_group(self, kg, lists, elems):
@@ -265,7 +305,7 @@ class GpuListWindowOperator:
     def initialize_state(self, snapshot):
         for kg, (lists, elems) in snapshot.items():
             if kg in self.key_group_range and len(lists):
-                self.restore_key_group(kg, lists, elems)
+                (self.restore_sessions_key_group if self.merging_state else self.restore_key_group)(kg, lists, elems)
 
     snapshotState, initializeState = snapshot_state, initialize_state
 

@@ -617,7 +617,10 @@ typedef struct fw_list_config {
   int32_t key_group_start;
   int32_t key_group_end;
   int32_t device;
-  int32_t pad0;
+  int32_t merging_state;     /* FW_SESSION only (FW_ERR_ARG otherwise): 1 = the handle keeps the full
+                                MergingWindowSet form per in-flight window (its state window, the trigger's
+                                count), takes FW_TRIGGER_COUNT and offers fw_list_snapshot_sessions /
+                                fw_list_restore_sessions.  0 (the slot was padding): nothing of it         */
   int64_t size, slide, offset, allowed_lateness;
   int64_t trigger_count;     /* CountTrigger.of(n)                                                */
   int64_t evict_count;       /* CountEvictor maxCount, TimeEvictor windowSize (ms)                */
@@ -673,6 +676,37 @@ int fw_list_snapshot_key_group(fw_list* op, int32_t key_group, const fw_list_sta
                                int64_t cap_elems, int64_t* n_lists, int64_t* n_elems);
 int fw_list_restore_key_group(fw_list* op, int32_t key_group, const fw_list_state* src, int64_t n_lists,
                               int64_t n_elems);
+
+/* Session windows (FW_SESSION handles created with merging_state = 1): a key group's keyed state in the form the
+ * merging WindowOperator keeps it (MergingWindowSet.java:150-225, WindowOperator.java:297-370): per in-flight window
+ * the window itself (the namespace of the trigger's state and of the timers), its state window (the namespace its
+ * "window-contents" list is kept under: the window the session started as, or the one a merge chose), the trigger's
+ * state (CountTrigger's count, CountTrigger.java:47-85; ContinuousEventTimeTrigger's fire time, Long.MIN_VALUE =
+ * null; 0 under EventTimeTrigger), timer with the bits of fw_list_state, and its list: the elements of all windows
+ * concatenated in list order (the order the window function sees, not arrival order).  A purged window is a row with
+ * n_elems 0: it stays in the MergingWindowSet until its cleanup time.
+ * CountTrigger over sessions (merging_state handles only): a merge sums the merged windows' counts into the result
+ * and does not fire; the element then counts, and at n the count is cleared and the window's whole list fires
+ * (evictors as for every firing; PurgingTrigger clears the list); no timer is registered, and the window, its list
+ * and its count are dropped at its cleanup time without a firing.
+ * fw_list_snapshot_sessions follows fw_list_snapshot_key_group: dst NULL or a capacity too small returns only the
+ * counts; windows come out in no particular order.  fw_list_restore_sessions refuses, with the handle untouched:
+ * lengths that do not add up, a window shorter than the gap, two windows of a key that intersect
+ * (TimeWindow.intersects) or share a state window, timer bits or a count that the handle's trigger cannot have
+ * (FW_ERR_ARG); a FW_KEY_LONG / FW_KEY_INT key outside key_group (FW_ERR_KEY_GROUP); a key that already has an
+ * in-flight window in the handle (FW_ERR_STATE).  Later pushes are numbered after the largest restored ordinal;
+ * windows that are already due fire or leave with the next fw_list_advance_watermark.  The watermark is not part of
+ * the state: a restored handle starts at Long.MIN_VALUE, as the reference's operator does, until it is advanced.  A
+ * device failure after the restore began to apply leaves the handle unusable (FW_ERR_STATE from then on).  Both return
+ * FW_ERR_UNSUPPORTED on a handle without merging_state. */
+typedef struct fw_session_state {
+  int64_t *key, *start, *end, *state_start, *state_end, *trigger_state, *timer, *n_elems; /* per window */
+  int64_t *ts, *val, *ordinal;                                                            /* elements   */
+} fw_session_state;
+int fw_list_snapshot_sessions(fw_list* op, int32_t key_group, const fw_session_state* dst, int64_t cap_windows,
+                              int64_t cap_elems, int64_t* n_windows, int64_t* n_elems);
+int fw_list_restore_sessions(fw_list* op, int32_t key_group, const fw_session_state* src, int64_t n_windows,
+                             int64_t n_elems);
 
 /* Count windows (an fw_op with FW_COUNT): the keyed state of one key group, in the logical form of the list operator
  * above, so it moves between count handles of any parallelism and to and from the equivalent fw_list handle

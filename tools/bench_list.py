@@ -31,8 +31,13 @@ def main():
     ap.add_argument("--rate", type=int, default=100_000_000)
     ap.add_argument("--window", type=int, default=1000)
     ap.add_argument("--evictor", default="none", help="none | count:N | time:MS")
-    ap.add_argument("--trigger", default="event_time", choices=["event_time", "continuous"],
-                    help="continuous: ContinuousEventTimeTrigger.of(--interval), early firings of every window")
+    ap.add_argument("--trigger", default="event_time",
+                    help="event_time | continuous: ContinuousEventTimeTrigger.of(--interval), early firings of every "
+                         "window | count:N: CountTrigger.of(N), with --sessions only (a merging_state handle)")
+    ap.add_argument("--sessions", type=int, default=0, metavar="GAP",
+                    help="EventTimeSessionWindows.withGap(GAP ms) instead of the tumbling windows")
+    ap.add_argument("--merging-state", action="store_true",
+                    help="with --sessions: the handle keeps the MergingWindowSet form (implied by --trigger count:N)")
     ap.add_argument("--interval", type=int, default=250, help="ContinuousEventTimeTrigger's interval, ms")
     ap.add_argument("--cpu-sample", type=int, default=1 << 22)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -40,7 +45,8 @@ def main():
 
     import numpy as np
     import torch
-    from flink_amd import ContinuousEventTimeTrigger, CountEvictor, TimeEvictor, TumblingEventTimeWindows
+    from flink_amd import (ContinuousEventTimeTrigger, CountEvictor, CountTrigger, EventTimeSessionWindows, TimeEvictor,
+                           TumblingEventTimeWindows)
     from flink_amd.datagen import generate_device
     from flink_amd.listwindow import GpuListWindowOperator
 
@@ -50,11 +56,20 @@ def main():
     elif args.evictor.startswith("time:"):
         ev = TimeEvictor.of(int(args.evictor[5:]))
     per_window = args.rate * args.window // 1000
-    trig = ContinuousEventTimeTrigger.of(args.interval) if args.trigger == "continuous" else None
+    if args.trigger.startswith("count:"):
+        if not args.sessions:
+            ap.error("--trigger count:N is measured over --sessions")
+        trig, args.merging_state = CountTrigger.of(int(args.trigger[6:])), True
+    elif args.trigger in ("event_time", "continuous"):
+        trig = ContinuousEventTimeTrigger.of(args.interval) if args.trigger == "continuous" else None
+    else:
+        ap.error("--trigger: event_time, continuous or count:N")
     if trig is not None:
-        args.no_cpu_baseline = True  # (the ListState oracle has no such trigger)
-    op = GpuListWindowOperator(TumblingEventTimeWindows.of(args.window), trigger=trig, evictor=ev, max_batch=args.batch,
-                               expected_elements=int(per_window * 1.3))
+        args.no_cpu_baseline = True  # (the ListState oracle has neither trigger: no CPU leg for them)
+    assigner = EventTimeSessionWindows.with_gap(args.sessions) if args.sessions else TumblingEventTimeWindows.of(args.window)
+    extra = {"merging_state": True} if args.merging_state else {}
+    op = GpuListWindowOperator(assigner, trigger=trig, evictor=ev, max_batch=args.batch,
+                               expected_elements=int(per_window * 1.3), **extra)
     dev = torch.device("cuda", 0)
     batches, wms, m = [], [], -(1 << 63)
     for s in range(args.warmup + args.steps):
@@ -93,7 +108,8 @@ def main():
         from flink_amd.datagen import generate_host
         from oracle import oracle as orc
         hk, ht, hv = generate_host(0x5EED, 0, args.cpu_sample, args.keys, ts_base=0, rate=args.rate, jitter=200)
-        ref = orc.ListWindowOracle(assigner="tumbling", size=args.window,
+        ref = orc.ListWindowOracle(assigner="session" if args.sessions else "tumbling", size=args.window,
+                                   gap=args.sessions,
                                    evictor="none" if ev is None else ("count" if args.evictor.startswith("count")
                                                                       else "time"),
                                    evict_arg=0 if ev is None else int(args.evictor.split(":")[1]))
@@ -114,8 +130,11 @@ def main():
         "unit": "records/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "dtype": "int64",
         "data": "synthetic (splitmix64 counter stream)",
-        "config": {"workload": f"f4: tumbling {args.window} ms apply over ListState, evictor {args.evictor}, "
-                               + (f"ContinuousEventTimeTrigger({args.interval} ms), " if trig is not None else "") +
+        "config": {"workload": "f4: " + (f"session gap {args.sessions} ms" + (", merging_state" if args.merging_state
+                                                                                 else "")
+                                        if args.sessions else f"tumbling {args.window} ms") +
+                               f" apply over ListState, evictor {args.evictor}, trigger {args.trigger}, "
+                               + (f"ContinuousEventTimeTrigger({args.interval} ms), " if args.trigger == "continuous" else "") +
                                f"{args.keys} uniform Long keys, {args.rate} records per event-second, 2^24 per step",
                    "fired_rows": fired, "fired_elements": elems, "table_grows": st["table_grows"]},
         "path_roofline": {"b_alg_bytes_per_record": B_ALG, "frac": round(B_ALG * value / 8e12, 4),
