@@ -238,8 +238,9 @@ __global__ void k_wire_counts(const uint8_t* __restrict__ entry, const uint32_t*
 struct WireOut {
   int64_t *key, *ts, *val;
   int32_t* kh;              // the key's hash (String.hashCode of a String key), or nullptr
-  int64_t* chunk_wm;        // per chunk: its last watermark, or INT64_MIN
-  int64_t* chunk_status;    // per chunk: its last stream status, or INT64_MIN
+  int64_t* chunk_wm;        // per chunk: its last watermark (any long, Long.MIN_VALUE included), if chunk_has & 1
+  int64_t* chunk_status;    // per chunk: its last stream status, if chunk_has & 2
+  uint32_t* chunk_has;      // per chunk: bit 0 it carried a watermark, bit 1 a stream status
   unsigned long long* acc;  // [0] watermarks, [1] latency markers, [2] statuses, [3] consumed (min over END walks),
                             // [4] first corrupt element (min), [5] its tag + 8
 };
@@ -255,7 +256,7 @@ __global__ __launch_bounds__(WE) void k_wire_emit(const uint8_t* __restrict__ b,
   __shared__ int ne;
   if (threadIdx.x == 0) {
     int k = 0, r = 0, wms = 0, lats = 0, sts = 0;
-    int64_t wm = INT64_MIN, status = INT64_MIN;
+    int64_t wm = 0, status = 0;
     if (entry[c] < X_END) {
       int64_t pos = cs + entry[c];
       while (pos < ce) {
@@ -289,6 +290,7 @@ __global__ __launch_bounds__(WE) void k_wire_emit(const uint8_t* __restrict__ b,
     ne = k;
     o.chunk_wm[c] = wm;
     o.chunk_status[c] = status;
+    o.chunk_has[c] = (wms ? 1u : 0u) | (sts ? 2u : 0u);
     if (wms) atomicAdd(&o.acc[0], (unsigned long long)wms);
     if (lats) atomicAdd(&o.acc[1], (unsigned long long)lats);
     if (sts) atomicAdd(&o.acc[2], (unsigned long long)sts);
@@ -330,8 +332,9 @@ __global__ __launch_bounds__(1024) void k_wire_final(const uint8_t* __restrict__
   }
   __syncthreads();
   for (int64_t c = threadIdx.x; c < nchunks; c += blockDim.x) {
-    if (o.chunk_wm[c] != INT64_MIN) atomicMax(&cw, (long long)c);
-    if (o.chunk_status[c] != INT64_MIN) atomicMax(&cs_, (long long)c);
+    const uint32_t has = o.chunk_has[c];  // by presence: Watermark(Long.MIN_VALUE) is a watermark like any other
+    if (has & 1u) atomicMax(&cw, (long long)c);
+    if (has & 2u) atomicMax(&cs_, (long long)c);
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -357,7 +360,8 @@ __global__ void k_wire_encode(DevRows rows, int64_t n, WireL L, int32_t f64, uin
   // window.maxTimestamp(): end - 1 for a TimeWindow (TimeWindow.java:83-85), Long.MAX_VALUE for the GlobalWindow
   // of a count window (GlobalWindow.java:45-46; its rows carry end = Long.MAX_VALUE)
   const int64_t end = rows.end[r];
-  st_be(p + 5, (uint64_t)(end == INT64_MAX ? end : end - 1), 8);
+  // (Java's long arithmetic wraps: Long.MIN_VALUE - 1 is Long.MAX_VALUE)
+  st_be(p + 5, end == INT64_MAX ? (uint64_t)end : (uint64_t)end - 1u, 8);
   for (int f = 0; f < L.nf; f++) {
     const int role = L.role[f];
     int64_t v = role == FW_ROLE_KEY ? rows.key[r] : role == FW_ROLE_START ? rows.start[r]
@@ -373,13 +377,21 @@ __global__ void k_wire_encode(DevRows rows, int64_t n, WireL L, int32_t f64, uin
     }
     uint8_t* q = p + 13 + L.off[f];
     switch (L.kind[f]) {
-      case FW_WIRE_LONG:
-      case FW_WIRE_DOUBLE: st_be(q, (uint64_t)v, 8); break;
+      case FW_WIRE_LONG: st_be(q, (uint64_t)v, 8); break;
+      case FW_WIRE_DOUBLE: {  // Double.doubleToLongBits: every NaN is 0x7ff8000000000000 (DataOutputSerializer.java:174)
+        const double d = __longlong_as_double(v);
+        st_be(q, d != d ? 0x7ff8000000000000ull : (uint64_t)v, 8);
+        break;
+      }
       case FW_WIRE_INT: st_be(q, (uint32_t)v, 4); break;
       case FW_WIRE_SHORT: st_be(q, (uint16_t)v, 2); break;
       case FW_WIRE_BYTE:
       case FW_WIRE_BOOL: q[0] = (uint8_t)v; break;
-      case FW_WIRE_FLOAT: st_be(q, (uint32_t)__float_as_int((float)__longlong_as_double(v)), 4); break;
+      case FW_WIRE_FLOAT: {  // Float.floatToIntBits((float) d): every NaN is 0x7fc00000 (DataOutputSerializer.java:179)
+        const float x = (float)__longlong_as_double(v);
+        st_be(q, x != x ? 0x7fc00000u : (uint32_t)__float_as_int(x), 4);
+        break;
+      }
     }
   }
 }
@@ -400,6 +412,7 @@ struct fw_wire {
   uint32_t *cnt = nullptr, *scan_tmp = nullptr;
   int64_t* chunk_wm = nullptr;
   int64_t* chunk_status = nullptr;
+  uint32_t* chunk_has = nullptr;
   unsigned long long* acc = nullptr;
   int64_t* last = nullptr;
   int64_t* h_tot = nullptr;  // pinned: records, then acc[0..5], last[0..2]
@@ -483,6 +496,7 @@ int fw_wire_create(const fw_wire_layout* layout, int64_t max_bytes, int32_t devi
   WIRE_HIP(w, hipMalloc(&w->scan_tmp, (size_t)((nc + 1) / 4096 + 2) * sizeof(uint32_t)));
   WIRE_HIP(w, hipMalloc(&w->chunk_wm, (size_t)nc * sizeof(int64_t)));
   WIRE_HIP(w, hipMalloc(&w->chunk_status, (size_t)nc * sizeof(int64_t)));
+  WIRE_HIP(w, hipMalloc(&w->chunk_has, (size_t)nc * sizeof(uint32_t)));
   WIRE_HIP(w, hipMalloc(&w->acc, 6 * sizeof(unsigned long long)));
   WIRE_HIP(w, hipMalloc(&w->last, 3 * sizeof(int64_t)));
   WIRE_HIP(w, hipHostMalloc(&w->h_tot, 16 * sizeof(int64_t)));
@@ -500,6 +514,7 @@ void fw_wire_destroy(fw_wire* w) {
   (void)hipFree(w->scan_tmp);
   (void)hipFree(w->chunk_wm);
   (void)hipFree(w->chunk_status);
+  (void)hipFree(w->chunk_has);
   (void)hipFree(w->acc);
   (void)hipFree(w->last);
   if (w->h_tot) (void)hipHostFree(w->h_tot);
@@ -554,7 +569,7 @@ int fw_wire_decode_keyed_device(fw_wire* w, const uint8_t* bytes, int64_t nbytes
                                                           " records, more than the output's capacity");
   unsigned long long init[6] = {0, 0, 0, (unsigned long long)nbytes, ~0ull, 0};
   WIRE_HIP(w, hipMemcpyAsync(w->acc, init, sizeof init, hipMemcpyHostToDevice, s));
-  WireOut o{key, ts, val, key_hash, w->chunk_wm, w->chunk_status, w->acc};
+  WireOut o{key, ts, val, key_hash, w->chunk_wm, w->chunk_status, w->chunk_has, w->acc};
   hipLaunchKernelGGL(k_wire_emit, dim3((unsigned)nc), dim3(WE), 0, s, bytes, nbytes, nc, w->dl, w->lentry[0], w->cnt, o);
   hipLaunchKernelGGL(k_wire_final, dim3(1), dim3(1024), 0, s, bytes, nc, o, w->last);
   WIRE_HIP(w, hipMemcpyAsync(w->h_tot + 1, w->acc, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, s));

@@ -83,7 +83,8 @@ class WireCodec:
     def decode(self, data, cap=None):
         """data: a CUDA uint8 tensor.  Returns (key, ts, val) int64 CUDA tensors (val holds double bits for Double /
         Float value fields), plus the int32 key_hash column when the key is a String, and the stats dict (records,
-        watermarks, latency_markers, statuses, consumed, watermark, status)."""
+        watermarks, latency_markers, statuses, consumed, watermark, status).  On a corrupt element the NativeError
+        carries `stats` (consumed = that element's byte position) and `columns` (the records before it)."""
         import torch
         n = data.numel()
         cap = n // (5 + self.value_bytes()) + 1 if cap is None else cap  # the smallest record element
@@ -92,12 +93,19 @@ class WireCodec:
         kh = torch.empty(cap, dtype=torch.int32, device=dev) if self.string_key() else None
         st = N.FwWireStats()
         torch.cuda.current_stream(dev).synchronize()  # the codec's stream reads the bytes
-        self._check(N.lib().fw_wire_decode_keyed_device(self._h, data.data_ptr(), n, key.data_ptr(),
-                                                        kh.data_ptr() if kh is not None else None, ts.data_ptr(),
-                                                        val.data_ptr(), cap, ctypes.byref(st)))
+        rc = N.lib().fw_wire_decode_keyed_device(self._h, data.data_ptr(), n, key.data_ptr(),
+                                                 kh.data_ptr() if kh is not None else None, ts.data_ptr(),
+                                                 val.data_ptr(), cap, ctypes.byref(st))
         r = st.records
         cols = (key[:r], ts[:r], val[:r]) + ((kh[:r],) if kh is not None else ())
-        return cols, {f: getattr(st, f) for f, _ in N.FwWireStats._fields_ if f != "pad"}
+        stats = {f: getattr(st, f) for f, _ in N.FwWireStats._fields_ if f != "pad"}
+        if rc != N.FW_OK:
+            err = N.NativeError(rc, N.lib().fw_wire_last_error(self._h).decode())
+            if rc == N.FW_ERR_STATE and "Corrupt stream" in str(err):
+                # the C-ABI filled the stats (consumed = the corrupt element's byte) and the records before it
+                err.stats, err.columns = stats, cols
+            raise err
+        return cols, stats
 
     def value_bytes(self):
         """The value's bytes (a String field counts its shortest form, one byte)."""

@@ -508,20 +508,34 @@ int fw_exchange_plan(int32_t world, int32_t rank, const int64_t* counts, int64_t
  * UTF-16 chars, then fmix64 of it ^ the length) and the key_hash column String.hashCode, the two columns
  * FW_KEY_HASHED takes; a null String key is a corrupt element (KeyGroupStreamPartitioner cannot hash it).  A
  * record with String fields is decoded when it is at most 64 bytes with its length prefix (WindowWordCount's
- * Tuple2<String, Integer> with a timestamp: words of up to 46 ASCII chars).
+ * Tuple2<String, Integer> with a timestamp: words of up to 46 ASCII chars); a longer one is refused as a corrupt
+ * element, and so is a String varint whose fifth byte still continues (writeString never writes one).  That limit,
+ * the integer narrowing below and the String key's id are this build's own; everything else is pinned against an
+ * independent restatement of the cited serializers (tests/wire_ref.py).
  *   fw_wire_decode_device: a device byte stream -> key / ts / val columns in arrival order (records without a
  *     timestamp get Long.MIN_VALUE, StreamRecord.getTimestamp), ready for fw_push_batch_device.  The field whose
  *     role is FW_ROLE_KEY becomes the key (an integer kind), FW_ROLE_VALUE the value (integers sign-extended,
  *     Double as its bits, Float widened to double bits); other fields are skipped.  stats: the frames of each
  *     kind, the last watermark (Long.MIN_VALUE if none: the caller's processWatermark), the last stream status
  *     (StreamStatus ACTIVE 0 / IDLE -1; 0 if none), and `consumed` = the bytes up to the end of the last complete element (a trailing partial element is
- *     the start of the next call's stream, SpillingAdaptiveSpanningRecordDeserializer's role).  Frames are
+ *     the start of the next call's stream, SpillingAdaptiveSpanningRecordDeserializer's role).  The last watermark
+ *     is found by presence: Watermark(Long.MIN_VALUE) is a watermark like any other.  At a corrupt element the
+ *     call returns FW_ERR_STATE and still fills `stats` (the frames before that element, `consumed` = its byte
+ *     position) and the columns' leading `stats->records` records, as the reference's deserializer has handed
+ *     those on before it throws.  Frames are
  *     found in parallel: every 2 KiB chunk is parsed from each of its 64 possible first-frame offsets, and the
  *     chunks' transfer functions are composed (a decoded element is at most 64 bytes with its length prefix:
  *     value fields of at most 51 bytes).
  *   fw_wire_encode_device: fired rows -> elements of one output channel: tag 0, timestamp = end - 1 (the
  *     window's maxTimestamp, WindowOperator.emitWindowContents' TimestampedCollector), a Tuple of the row
- *     fields the layout's roles name (FW_ROLE_KEY / START / END / COUNT / SUM / MIN / MAX).
+ *     fields the layout's roles name (FW_ROLE_KEY / START / END / COUNT / SUM / MIN / MAX).  end - 1 is Java's
+ *     long arithmetic (Long.MIN_VALUE - 1 wraps to Long.MAX_VALUE); a row whose end is Long.MAX_VALUE is a
+ *     GlobalWindow's and keeps Long.MAX_VALUE (GlobalWindow.java:45-46).  Double and Float fields are written as
+ *     DataOutputSerializer does (doubleToLongBits / floatToIntBits, DataOutputSerializer.java:173-180): every NaN,
+ *     whatever its sign and payload, becomes 0x7ff8000000000000 / 0x7fc00000, and (float) rounds to nearest even.
+ *     An integer row field written into a Double / Float field is (double) v, then (float) of that.  An f64 row
+ *     field (sum / min / max of an FW_VAL_F64 aggregate) written into an integer field is Java's (long) d (NaN 0,
+ *     saturating, toward zero) and then the field's low bytes, as (int) / (short) / (byte) of that long.
  * Both return FW_ERR_ARG for an unsupported layout and FW_ERR_STATE for a corrupt stream (message in
  * fw_wire_last_error) or too small an output; they run on the codec's own stream and return when done. */
 #define FW_WIRE_LONG 0

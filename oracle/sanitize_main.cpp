@@ -6,7 +6,9 @@
 // baseline) on a seeded stream with extreme keys and timestamps, and checks the host-side arithmetic the
 // library shares with the device code (make_div_inv, flink_amd/csrc/fw_internal.h) against 128-bit division, and
 // at both ends of the long range the window start, the host's FW_ERR_TIME_RANGE refusals and the compact records' base
-// (flink_amd/csrc/fw_range.h) against 128-bit restatements and the oracle.
+// (flink_amd/csrc/fw_range.h) against 128-bit restatements and the oracle.  It also drives the wire oracle
+// (wire_oracle.cpp): a mixed stream cut at every byte (each prefix in a heap block of exactly its size, so a read
+// past it is seen), corrupt String records, and rows whose `end` and NaN sums sit at the ends of their ranges.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +17,7 @@
 #include "../flink_amd/csrc/fw_internal.h"
 #include "../flink_amd/csrc/fw_range.h"
 #include "window_oracle.h"
+#include "wire_oracle.h"
 
 static uint64_t sm(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;
@@ -260,7 +263,143 @@ static void run(oracle_cfg cfg, int n, uint64_t seed) {
   oracle_destroy(op);
 }
 
+// ---- the wire oracle
+static void put_bytes(std::vector<uint8_t>& v, std::initializer_list<int> bs) {
+  for (int b : bs) v.push_back((uint8_t)b);
+}
+// one element: the 4-byte length of the parts' bytes, then those bytes
+static std::vector<uint8_t> framed(std::initializer_list<std::initializer_list<int>> parts) {
+  std::vector<uint8_t> v = {0, 0, 0, 0};
+  for (const auto& p : parts) put_bytes(v, p);
+  v[3] = (uint8_t)(v.size() - 4);
+  return v;
+}
+// decode `n` bytes from a heap block of exactly n bytes
+static int decode_exact(const uint8_t* src, int64_t n, const oracle_wire_layout* L, oracle_wire_stats* st, int64_t* recs) {
+  uint8_t* blk = (uint8_t*)malloc(n ? (size_t)n : 1);
+  if (n) memcpy(blk, src, (size_t)n);
+  const int64_t cap = n / 5 + 1;
+  std::vector<int64_t> k((size_t)cap), t((size_t)cap), v((size_t)cap);
+  std::vector<int32_t> h((size_t)cap);
+  const int rc = oracle_wire_decode_keyed(n ? blk : nullptr, n, L, k.data(), h.data(), t.data(), v.data(), cap, st);
+  if (recs) *recs = st->records;
+  free(blk);
+  return rc;
+}
+static int check_wire() {
+  int bad = 0;
+  const oracle_wire_layout F3{3, {OR_WIRE_LONG, OR_WIRE_LONG, OR_WIRE_INT}, {OR_ROLE_KEY, OR_ROLE_SKIP, OR_ROLE_VALUE}};
+  const oracle_wire_layout S4{4, {OR_WIRE_LONG, OR_WIRE_STRING, OR_WIRE_STRING, OR_WIRE_INT},
+                              {OR_ROLE_SKIP, OR_ROLE_KEY, OR_ROLE_SKIP, OR_ROLE_VALUE}};
+  const oracle_wire_layout S2{2, {OR_WIRE_STRING, OR_WIRE_INT}, {OR_ROLE_KEY, OR_ROLE_VALUE}};
+  {  // a mixed stream of every element kind, cut at every byte: records and consumed never shrink, nothing is corrupt
+    std::vector<uint8_t> b(64 * 40);
+    int64_t n = 0;
+    for (int i = 0; i < 60; i++) {
+      const int64_t f[3] = {i % 2 ? INT64_MIN : INT64_MAX - i, -i, i * 77};
+      switch (i % 5) {
+        case 0: n += oracle_wire_put_record(&F3, 1, i % 10 ? i : INT64_MIN, f, b.data() + n); break;
+        case 1: n += oracle_wire_put_record(&F3, 0, 0, f, b.data() + n); break;
+        case 2: n += oracle_wire_put_watermark(i == 57 ? INT64_MIN : i, b.data() + n); break;
+        case 3: n += oracle_wire_put_latency(i, INT64_MIN, INT64_MAX, i, b.data() + n); break;
+        default: n += oracle_wire_put_status(i == 59 ? INT32_MIN : -(i & 1), b.data() + n); break;
+      }
+    }
+    int64_t last_recs = 0, last_cons = 0;
+    for (int64_t cut = 0; cut <= n; cut++) {
+      oracle_wire_stats st;
+      int64_t recs = 0;
+      if (decode_exact(b.data(), cut, &F3, &st, &recs) != 0) bad++;
+      if (recs < last_recs || st.consumed < last_cons || st.consumed > cut) bad++;
+      last_recs = recs;
+      last_cons = st.consumed;
+      if (cut == n && (st.consumed != n || recs != 24 || st.watermark != INT64_MIN || st.status != INT32_MIN)) bad++;
+    }
+    for (int tag : {5, 0x80, 0xff}) {  // an unknown tag, also as the very last byte of the block
+      std::vector<uint8_t> c(b.begin(), b.begin() + 33);
+      put_bytes(c, {0, 0, 0, 1, tag});
+      oracle_wire_stats st;
+      if (decode_exact(c.data(), (int64_t)c.size(), &F3, &st, nullptr) != -1 || st.bad_tag != (int8_t)tag || st.consumed != 33) bad++;
+    }
+    std::vector<uint8_t> e = {0, 0, 0, 0};  // an empty element
+    oracle_wire_stats st;
+    if (decode_exact(e.data(), 4, &F3, &st, nullptr) != -1 || st.bad_tag != -3) bad++;
+  }
+  {  // String records: good ones cut at every byte, then the corruptions (each must be refused, none read past its end)
+    const std::initializer_list<int> ts9 = {0, 0, 0, 0, 0, 0, 0, 0, 9};  // tag 0 and its timestamp
+    std::vector<uint8_t> g = framed({ts9, {1, 2, 3, 4, 5, 6, 7, 8, 3, 'a', 0xe5, 0xcb, 0x01, 0, 0, 0, 0, 7}});
+    const std::vector<uint8_t> g2 = framed({{1, 1, 2, 3, 4, 5, 6, 7, 8, 1, 4, 0xff, 0xff, 0x03, 'x', 'y', 0, 0, 0, 7}});
+    g.insert(g.end(), g2.begin(), g2.end());
+    for (int64_t cut = 0; cut <= (int64_t)g.size(); cut++) {
+      oracle_wire_stats st;
+      int64_t recs = 0;
+      if (decode_exact(g.data(), cut, &S4, &st, &recs) != 0) bad++;
+      if (cut == (int64_t)g.size() && (recs != 2 || st.consumed != cut)) bad++;
+    }
+    const std::vector<std::vector<uint8_t>> corrupt = {
+        framed({ts9, {3, 'a', 0xe5}}),                                               // a char's varint runs past the element
+        framed({ts9, {0x83}}),                                                       // the length's varint does
+        framed({ts9, {3, 'a', 'b', 0, 0, 0, 7, 0}}),                                 // the String ends before the element
+        framed({ts9, {6, 'a', 'b'}}),                                                // ... and after it
+        framed({ts9, {2, 0x81, 0x80, 0x80, 0x80, 0x80, 0, 0, 0, 0, 7}}),             // a fifth byte that continues
+        framed({ts9, {2, 0x81, 0x80, 0x80, 0x80, 0x80, 0x80, 0x80, 0, 0, 0, 0, 7}}),
+        framed({ts9, {0xff, 0xff, 0xff, 0xff, 0x0f, 'a', 'b', 0, 0, 0, 7}}),         // a huge length
+        framed({{0, 1, 2}}),                                                         // no room for the timestamp
+    };
+    for (const auto& v : corrupt) {
+      oracle_wire_stats st;
+      if (decode_exact(v.data(), (int64_t)v.size(), &S2, &st, nullptr) != -1 || st.bad_tag != -2 || st.consumed != 0) bad++;
+    }
+    const std::vector<uint8_t> nk = framed({ts9, {0, 0, 0, 0, 7}});  // a null String key
+    oracle_wire_stats st;
+    if (decode_exact(nk.data(), (int64_t)nk.size(), &S2, &st, nullptr) != -1 || st.bad_tag != -4) bad++;
+  }
+  {  // encode: `end` at both ends of the long range (end - 1 wraps as Java's does), NaN and out-of-range sums
+    const oracle_wire_layout out{6, {OR_WIRE_DOUBLE, OR_WIRE_FLOAT, OR_WIRE_LONG, OR_WIRE_INT, OR_WIRE_SHORT, OR_WIRE_BYTE},
+                                 {OR_ROLE_SUM, OR_ROLE_SUM, OR_ROLE_SUM, OR_ROLE_MIN, OR_ROLE_MAX, OR_ROLE_END}};
+    const uint64_t sums[] = {0x7ff8000000000000ull, 0xfff8000000000000ull, 0x7ff0000000000001ull, 0xffffffffffffffffull,
+                             0x43e0000000000000ull /* 2^63 */, 0xc3e0000000000001ull, 0x7fe1ccf385ebc8a0ull /* 1e308 */,
+                             0xfff0000000000000ull, 0x0000000000000001ull, 0x47efffffe0000000ull /* FLT_MAX */};
+    const int64_t ends[] = {3000, INT64_MAX, INT64_MIN, 0, INT64_MIN + 1};
+    std::vector<oracle_row> rows;
+    for (uint64_t sb : sums)
+      for (int64_t e : ends) {
+        oracle_row r{};
+        r.end = e;
+        r.start = e;
+        memcpy(&r.sum, &sb, 8);
+        r.min = r.sum;
+        r.max = r.sum;
+        rows.push_back(r);
+      }
+    for (int f64 = 0; f64 <= 1; f64++) {
+      const int64_t S = 13 + 27, n = (int64_t)rows.size();
+      uint8_t* o = (uint8_t*)malloc((size_t)(n * S));
+      if (oracle_wire_encode(&out, rows.data(), n, f64, o, n * S) != n * S) bad++;
+      if (oracle_wire_encode(&out, rows.data(), n, f64, o, n * S - 1) != -1) bad++;
+      for (int64_t r = 0; r < n; r++) {
+        uint64_t ts = 0, d = 0;
+        for (int i = 0; i < 8; i++) {
+          ts = (ts << 8) | o[r * S + 5 + i];
+          d = (d << 8) | o[r * S + 13 + i];
+        }
+        const int64_t e = rows[(size_t)r].end;
+        if (ts != (e == INT64_MAX ? (uint64_t)e : (uint64_t)e - 1u)) bad++;
+        const bool nan = (d & 0x7ff0000000000000ull) == 0x7ff0000000000000ull && (d & 0x000fffffffffffffull);
+        if (nan && d != 0x7ff8000000000000ull) bad++;  // Double.doubleToLongBits
+      }
+      free(o);
+    }
+  }
+  return bad;
+}
+
 int main() {
+  const int bad_wire = check_wire();
+  if (bad_wire) {
+    fprintf(stderr, "the wire oracle: %d wrong\n", bad_wire);
+    return 1;
+  }
   const int bad = check_div_inv();
   if (bad) {
     fprintf(stderr, "make_div_inv: %d wrong quotients\n", bad);

@@ -48,6 +48,9 @@ int64_t read_varint(const uint8_t* p, const uint8_t* end, uint32_t* out) {
       if (q >= end) return -1;
       curr = *q++;
       if (curr < 0x80) break;
+      // a fifth byte that still continues: writeString never writes one (an int has five base-128 groups), and a
+      // sixth group would shift by 35
+      if (shift >= 28) return -1;
       v |= (curr & 0x7f) << shift;
       shift += 7;
     }
@@ -115,8 +118,13 @@ int64_t field_value(int32_t kind, const uint8_t* p) {
 }
 void put_field(int32_t kind, uint8_t* p, int64_t v) {
   switch (kind) {
-    case OR_WIRE_LONG:
-    case OR_WIRE_DOUBLE: put_be(p, (uint64_t)v, 8); break;
+    case OR_WIRE_LONG: put_be(p, (uint64_t)v, 8); break;
+    case OR_WIRE_DOUBLE: {  // Double.doubleToLongBits: every NaN is 0x7ff8000000000000 (DataOutputSerializer.java:174)
+      double d;
+      std::memcpy(&d, &v, 8);
+      put_be(p, d != d ? 0x7ff8000000000000ull : (uint64_t)v, 8);
+      break;
+    }
     case OR_WIRE_INT: put_be(p, (uint32_t)v, 4); break;
     case OR_WIRE_SHORT: put_be(p, (uint16_t)v, 2); break;
     case OR_WIRE_BYTE:
@@ -127,6 +135,7 @@ void put_field(int32_t kind, uint8_t* p, int64_t v) {
       const float f = (float)d;
       uint32_t b;
       std::memcpy(&b, &f, 4);
+      if (f != f) b = 0x7fc00000u;  // every NaN (DataOutputSerializer.java:179)
       put_be(p, b, 4);
       break;
     }
@@ -248,7 +257,8 @@ int64_t oracle_wire_encode(const oracle_wire_layout* L, const oracle_row* rows, 
     p[4] = 0;
     // window.maxTimestamp(): TimeWindow end - 1 (TimeWindow.java:83-85); GlobalWindow Long.MAX_VALUE
     // (GlobalWindow.java:45-46, count-window rows carry end = Long.MAX_VALUE)
-    put_be(p + 5, (uint64_t)(rows[r].end == INT64_MAX ? rows[r].end : rows[r].end - 1), 8);
+    // (Java's long arithmetic wraps: Long.MIN_VALUE - 1 is Long.MAX_VALUE)
+    put_be(p + 5, rows[r].end == INT64_MAX ? (uint64_t)rows[r].end : (uint64_t)rows[r].end - 1u, 8);
     uint8_t* f = p + 13;
     for (int i = 0; i < L->nfields; i++) {
       const oracle_row& w = rows[r];

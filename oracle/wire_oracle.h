@@ -23,7 +23,10 @@
  *   StreamRecord.getTimestamp of a record without timestamp = Long.MIN_VALUE (StreamRecord.java:91-100).
  *   WindowOperator.emitWindowContents: the row's timestamp is the window's maxTimestamp = end - 1.
  * Pinned by the big-endian TimeWindow / timer longs inside the reference's own win-op-migration snapshot
- * (tests/golden/wire_fixture.json) and by round trips. */
+ * (tests/golden/wire_fixture.json), by round trips, and byte for byte by tests/wire_ref.py, an independent Python
+ * restatement of the same sources (tests/test_oracle_wire_edges.py).  Double / Float fields are written with
+ * doubleToLongBits / floatToIntBits' canonical NaN; unlike the library the oracle reads a String record of any
+ * length (the 64-byte limit is the library's own). */
 #pragma once
 #include <stdint.h>
 #include "window_oracle.h"
@@ -45,7 +48,8 @@ typedef struct {
   int64_t consumed;
   int64_t watermark;
   int32_t status;
-  int32_t bad_tag;  /* the corrupt tag (or -2 for an element that does not fit the layout, -4 for a null String
+  int32_t bad_tag;  /* the corrupt tag (or -2 for an element that does not fit the layout -- a String varint whose
+                       fifth byte still continues included --, -3 for an empty element, -4 for a null String
                        key), when decode returns -1 */
 } oracle_wire_stats;
 /* 0 = ok, -1 = corrupt stream (stats->bad_tag), -2 = more records than cap, -3 = a String key without key_hash */
