@@ -46,7 +46,7 @@ class FwConfig(ctypes.Structure):
                 ("tdigest_quantiles", ctypes.c_double * 3), ("count_evict_after", ctypes.c_int32),
                 ("pad0", ctypes.c_int32), ("row_columns", ctypes.c_int32), ("row_aggregates", ctypes.c_int32),
                 ("row_column_type", ctypes.c_int32 * 8), ("row_aggregate", ctypes.c_int32 * 16),
-                ("no_panes", ctypes.c_int32), ("pad1", ctypes.c_int32)]
+                ("no_panes", ctypes.c_int32), ("trigger", ctypes.c_int32), ("trigger_interval", ctypes.c_int64)]
 
 
 class FwRows(ctypes.Structure):
@@ -172,6 +172,10 @@ SIGNATURES = {
                                                     ctypes.c_int64, I64P]),
     "fw_restore_key_group_blocks": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwStateRows), VP,
                                                    ctypes.c_int64]),
+    "fw_snapshot_key_group_fire": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwStateRows), VP,
+                                                  ctypes.c_int64, I64P]),
+    "fw_restore_key_group_fire": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwStateRows), VP,
+                                                 ctypes.c_int64]),
     "fw_key_groups_device": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, VP, VP]),
     "fw_route_device": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_int32, VP, VP, VP, VP, VP, VP, ctypes.c_int64, VP]),

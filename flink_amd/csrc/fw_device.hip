@@ -21,6 +21,8 @@
 //   k_fire            — HeapInternalTimerService.advanceWatermark as a scan/compaction: every region
 //                       whose earliest timer is <= wm emits its fired windows and is rebuilt, without
 //                       the cleaned-up entries, into the region's other buffer.
+// ContinuousEventTimeTrigger handles (cont_iv()) run the _cont instantiations of the push kernels, arm their
+// windows behind the push (k_ca_first / k_ca_arm) and fire with k_cf_count / k_cf_fire ("ContinuousEventTimeTrigger").
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -28,6 +30,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "../../include/flink_window.h"
+#include "fw_cont.h"
 #include "fw_internal.h"
 
 namespace {
@@ -207,6 +210,9 @@ __device__ __forceinline__ bool pane_range(const DevCfg& c, int64_t ts, int64_t 
 
 // class of a record against watermark wm; for CLS_NORMAL also its windows (newest start, count).
 // taint: the batch's Status.taint_any (sessions only).
+// CONT: a ContinuousEventTimeTrigger handle (tumbling / sliding windows kept as windows): a record whose first fire
+// time wraps past Long.MAX_VALUE is refused (fw_range.h fw_first_fire_wraps)
+template <bool CONT = false>
 __device__ __forceinline__ int classify(const DevCfg& c, int64_t wm, int64_t ts, int64_t* last_out = nullptr,
                                         int* k_out = nullptr, int64_t key = 0, int taint = 0) {
   if (c.assigner == FW_SESSION) {
@@ -240,6 +246,9 @@ __device__ __forceinline__ int classify(const DevCfg& c, int64_t wm, int64_t ts,
     if (pane_range(c, ts, last)) return CLS_RANGE;
     if (cleanup_of(jadd(last, c.size), 0) > wm) return CLS_NORMAL;
     return ts <= wm ? CLS_LATE : CLS_SKIP;
+  }
+  if constexpr (CONT) {
+    if (fw_first_fire_wraps(ts, cont_iv(c))) return CLS_RANGE;
   }
   int64_t last;
   int k = num_windows(c, ts, &last);
@@ -641,7 +650,7 @@ __device__ __forceinline__ int32_t tile_of_block(int32_t T) {
 // The streaming kernels are instantiated for the common shapes too: Long keys with tumbling windows, and Long
 // keys with panes.  The configuration is then known to the compiler (the generic instantiation's branches for
 // other assigners, key kinds and session taint drop out of the per-record loop).
-enum { M_GEN = 0, M_TUMB = 1, M_PANE = 2 };
+enum { M_GEN = 0, M_TUMB = 1, M_PANE = 2, M_CONT = 3 };  // M_CONT: M_GEN of a ContinuousEventTimeTrigger handle
 template <int MODE>
 __device__ __forceinline__ void specialize(DevCfg& c) {
   if constexpr (MODE == M_TUMB) {
@@ -656,6 +665,7 @@ __device__ __forceinline__ void specialize(DevCfg& c) {
   }
 }
 __host__ __forceinline__ int stream_mode(const DevCfg& c) {
+  if (cont_iv(c)) return M_CONT;
   if (c.key_kind != FW_KEY_LONG) return M_GEN;
   if (c.assigner == FW_TUMBLING) return M_TUMB;
   return c.panes ? M_PANE : M_GEN;
@@ -713,7 +723,7 @@ __global__ __launch_bounds__(FW_TILE_THREADS) void k_classify_hist(DevCfg c, int
       }
       int64_t last = 0;
       int nw = 0;
-      const int cls = classify(c, wm, t[j], &last, &nw, k[j], taint);
+      const int cls = classify<MODE == M_CONT>(c, wm, t[j], &last, &nw, k[j], taint);
       if (cls == CLS_NORMAL) {
         atomicAdd(&lh[p], 1u);
         if (c.compact && compact_delta(c, last) < 0) wide = 1;
@@ -887,6 +897,7 @@ __device__ __forceinline__ void store_pair(PRec* part, bool valid, uint32_t pos,
 // ---- K2: scatter.  Normal records -> their partition's run (any order inside the run), one
 // 32-byte sector per record; late records -> side output / counter.
 // (the body of one tile: base = P words of LDS for the runs' next free slots)
+template <bool CONT = false>
 __device__ __forceinline__ void scatter_direct(const DevCfg& c, int64_t wm, const int64_t* __restrict__ key,
                                                const int64_t* __restrict__ ts, const int64_t* __restrict__ val,
                                                const int32_t* __restrict__ kh, int64_t n, int32_t T,
@@ -914,7 +925,7 @@ __device__ __forceinline__ void scatter_direct(const DevCfg& c, int64_t wm, cons
         const int32_t h = c.key_kind == FW_KEY_HASHED ? hh[j] : key_hash_of(c.key_kind, k[j], kh, i);
         const int32_t p = partition_of(c, k[j], h);
         if (p >= 0) {
-          const int cls = classify(c, wm, t[j], &last, &nwin, k[j], taint);
+          const int cls = classify<CONT>(c, wm, t[j], &last, &nwin, k[j], taint);
           if (cls == CLS_NORMAL) {
             pos = atomicAdd(&base[p], 1u);
             norm = true;
@@ -975,7 +986,7 @@ __global__ __launch_bounds__(FW_TILE_THREADS, FW_SCATTER_WAVES) void k_scatter(D
                                                              DevSide side, Status* st) {
   specialize<MODE>(c);
   extern __shared__ uint32_t base[];  // P: next free slot of each partition's run for this tile
-  scatter_direct(c, wm, key, ts, val, kh, n, T, offs, part, side, st, base, tile_of_block(T));
+  scatter_direct<MODE == M_CONT>(c, wm, key, ts, val, kh, n, T, offs, part, side, st, base, tile_of_block(T));
 }
 
 // ---- K2, staged form (compact batches, P <= 2048).  The scattered 16-byte stores of k_scatter land as partial
@@ -1310,13 +1321,14 @@ __global__ __launch_bounds__(FW_TILE_THREADS) void k_scatter_rsv(DevCfg c, int64
 
 // ---- K2b: ordered compaction of the ordered-path records of a tile (skipped by tiles that have none).
 // srow: the scanned ordered-path counts per tile, then the raw counts.
-__global__ __launch_bounds__(FW_TILE_THREADS) void k_scatter_ordered(DevCfg c, int64_t wm, const int64_t* __restrict__ key,
-                                                                     const int64_t* __restrict__ ts,
-                                                                     const int64_t* __restrict__ val,
-                                                                     const int32_t* __restrict__ kh, int64_t n,
-                                                                     int32_t T, const uint32_t* __restrict__ srow,
-                                                                     int64_t* __restrict__ sk, int64_t* __restrict__ stt,
-                                                                     int64_t* __restrict__ sv, int32_t* __restrict__ skh, const Status* st) {
+// (CONT: the _cont kernel of a ContinuousEventTimeTrigger handle, classify<true>)
+template <bool CONT>
+__device__ __forceinline__ void scatter_ordered_body(DevCfg& c, int64_t wm, const int64_t* __restrict__ key,
+                                                     const int64_t* __restrict__ ts, const int64_t* __restrict__ val,
+                                                     const int32_t* __restrict__ kh, int64_t n, int32_t T,
+                                                     const uint32_t* __restrict__ srow, int64_t* __restrict__ sk,
+                                                     int64_t* __restrict__ stt, int64_t* __restrict__ sv,
+                                                     int32_t* __restrict__ skh, const Status* st) {
   const uint32_t* tile_slow = srow + T;
   if (tile_slow[blockIdx.x] == 0) return;
   const int taint = c.assigner == FW_SESSION ? st->taint_any : 0;
@@ -1340,7 +1352,7 @@ __global__ __launch_bounds__(FW_TILE_THREADS) void k_scatter_ordered(DevCfg c, i
       if (p >= 0) {
         int64_t last = 0;
         int nw = 0;
-        cls = classify(c, wm, t, &last, &nw, k, taint);
+        cls = classify<CONT>(c, wm, t, &last, &nw, k, taint);
       }
     }
     const bool is_slow = cls == CLS_SLOW;
@@ -1364,6 +1376,24 @@ __global__ __launch_bounds__(FW_TILE_THREADS) void k_scatter_ordered(DevCfg c, i
     running += tot;
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(FW_TILE_THREADS) void k_scatter_ordered(DevCfg c, int64_t wm, const int64_t* __restrict__ key,
+                                                                     const int64_t* __restrict__ ts,
+                                                                     const int64_t* __restrict__ val,
+                                                                     const int32_t* __restrict__ kh, int64_t n,
+                                                                     int32_t T, const uint32_t* __restrict__ srow,
+                                                                     int64_t* __restrict__ sk, int64_t* __restrict__ stt,
+                                                                     int64_t* __restrict__ sv, int32_t* __restrict__ skh, const Status* st) {
+  scatter_ordered_body<false>(c, wm, key, ts, val, kh, n, T, srow, sk, stt, sv, skh, st);
+}
+__global__ __launch_bounds__(FW_TILE_THREADS) void k_scatter_ordered_cont(DevCfg c, int64_t wm, const int64_t* __restrict__ key,
+                                                                          const int64_t* __restrict__ ts,
+                                                                          const int64_t* __restrict__ val,
+                                                                          const int32_t* __restrict__ kh, int64_t n,
+                                                                          int32_t T, const uint32_t* __restrict__ srow,
+                                                                          int64_t* __restrict__ sk, int64_t* __restrict__ stt,
+                                                                          int64_t* __restrict__ sv, int32_t* __restrict__ skh, const Status* st) {
+  scatter_ordered_body<true>(c, wm, key, ts, val, kh, n, T, srow, sk, stt, sv, skh, st);
 }
 
 // ---- K3: per-partition LDS pre-aggregation + flush into the HBM region.
@@ -3034,6 +3064,11 @@ __device__ __forceinline__ void td_chain_insert(const DevCfg& c, int32_t* head, 
 }
 
 // WindowOperator.processElement, non-merging branch (WindowOperator.java:371-407)
+// (CONT: a ContinuousEventTimeTrigger handle.  Its onElement fires at once exactly where EventTimeTrigger's does,
+// maxTimestamp <= watermark, and arms nothing then; the windows it does arm are armed behind the push, k_ca_arm.  A
+// window purged by such a firing keeps its entry, emptied, until its cleanup time: the trigger's fire time and the
+// timers outlive the purge.)
+template <bool CONT>
 __device__ void replay_time_windows(const SlowCtx& x, int32_t p, int64_t k, int64_t t, int64_t v, int64_t fo, bool* skipped) {
   const DevCfg& c = x.c;
   const Region r = region_of(c, x.tb, p, x.tb.cur[p]);
@@ -3055,14 +3090,19 @@ __device__ void replay_time_windows(const SlowCtx& x, int32_t p, int64_t k, int6
       ne.start = s;
       ne.end = e;
       acc_clear(c, ne);
-      ne.meta = c.pool_bytes ? (int64_t)(pool_new_block(c, x.st) << 1) : 0;
+      if constexpr (CONT)  // (count/sum/min/max only: nothing of the block-pool aggregates is instantiated)
+        ne.meta = 0;
+      else
+        ne.meta = c.pool_bytes ? (int64_t)(pool_new_block(c, x.st) << 1) : 0;
       slot = new_slot(x, r, p, h, ne);
       if (slot < 0) continue;
     }
     Entry en = r.ent[slot];
     acc_add(c, en, v, fo);
-    if (c.agg == FW_AGG_HLL) hll_raise(c, pool_block_of(en), v);  // (k_hll_update takes the partitioned records)
-    if (c.agg == FW_AGG_ROW) row_add(c, pool_block_of(en), v);   // (v: the record's index in the push)
+    if constexpr (!CONT) {
+      if (c.agg == FW_AGG_HLL) hll_raise(c, pool_block_of(en), v);  // (k_hll_update takes the partitioned records)
+      if (c.agg == FW_AGG_ROW) row_add(c, pool_block_of(en), v);   // (v: the record's index in the push)
+    }
     int32_t head = -1;
     if (td) {  // the window's chain of this push's values: this element on top
       if (oj < 0) {
@@ -3079,7 +3119,9 @@ __device__ void replay_time_windows(const SlowCtx& x, int32_t p, int64_t k, int6
     }
     bool keep = true;
     if (jsub(e, 1) <= x.wm) {  // EventTimeTrigger.onElement -> FIRE (WindowOperator.java:395-401)
-      if (td) {  // getResult over the centroids and the push's values so far (the window stays)
+      if constexpr (CONT) {
+        emit_one(c, x.out, x.st, en);
+      } else if (td) {  // getResult over the centroids and the push's values so far (the window stays)
         td_late_row(x, en, head);
       } else if (c.agg == FW_AGG_HLL) {  // getResult from the window's registers (the window stays unless purged)
         Entry fr = en;
@@ -3094,6 +3136,7 @@ __device__ void replay_time_windows(const SlowCtx& x, int32_t p, int64_t k, int6
     } else {
       en.meta |= FW_TIMER;  // registerEventTimeTimer(maxTimestamp)
     }
+    if constexpr (!CONT)
     if (!keep && (c.agg == FW_AGG_HLL || td)) {
       // the purged window keeps its slot and emptied block as empty state (cnt 0: nothing fires from it, and its GC
       // timer frees the block in k_fire): this kernel pops blocks for new windows, and a push beside those pops could
@@ -3106,6 +3149,12 @@ __device__ void replay_time_windows(const SlowCtx& x, int32_t p, int64_t k, int6
       acc_clear(c, en);
       en.meta &= ~(int64_t)FW_TIMER;
       keep = true;
+    }
+    if constexpr (CONT) {
+      if (!keep) {
+        acc_clear(c, en);
+        keep = true;
+      }
     }
     if (keep) {
       r.ent[slot] = en;
@@ -3267,118 +3316,26 @@ __device__ void replay_session(const SlowCtx& x, int32_t p, int64_t k, int64_t t
   note_timer(x, p, en);
 }
 
+// (the body: fw_slow_body.inc, once per kernel; k_slow_cont is the ContinuousEventTimeTrigger handles')
 __global__ __launch_bounds__(FW_SLOW_THREADS) void k_slow(DevCfg c, int64_t wm, const uint32_t* __restrict__ srow,
                                                           int32_t T, const int64_t* __restrict__ sk,
                                                           const int64_t* __restrict__ stt,
                                                           const int64_t* __restrict__ sv,
                                                           const int32_t* __restrict__ skh, DevTable tb, DevRows out,
                                                           DevSide side, Status* st, int resume) {
-  if (__hip_atomic_load(&st->suspended, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;  // resumed later
-  // list length: the ordered-path offset of the last tile plus that tile's own count
-  const int64_t n = (int64_t)(srow[T - 1] - srow[0]) + srow[T + T - 1];
-  const int64_t first = resume ? st->slow_resume : 0;
-  if (first >= n) return;
-  __shared__ int64_t ck[SLOW_CHUNK];
-  __shared__ int32_t ci[SLOW_CHUNK], cp[SLOW_CHUNK], cd[SLOW_CHUNK];
-  __shared__ int bad;
-  SlowCtx x{c, wm, tb, out, side, st};
-  unsigned long long late = 0;
-  const int tid = threadIdx.x;
-  const int64_t row_bound = c.assigner == FW_SESSION ? 1 : c.wpr;  // fired rows per record, at most
-  int64_t b0 = first;
-  for (; b0 < n; b0 += SLOW_CHUNK) {
-    const int m = (int)min((int64_t)SLOW_CHUNK, n - b0);
-    if (tid == 0) bad = 0;
-    if (tid < m) {
-      const int64_t i = b0 + tid;
-      ck[tid] = sk[i];
-      cp[tid] = partition_of(c, ck[tid], skh[i]);
-      int64_t last;
-      cd[tid] = c.assigner == FW_SESSION ? 1 : num_windows(c, stt[i], &last);  // new windows, at most
-      ci[tid] = tid;
-    } else {
-      ck[tid] = LMAX;
-      cp[tid] = INT32_MAX;
-      cd[tid] = 0;
-      ci[tid] = INT32_MAX;
-    }
-    __syncthreads();
-    // bitonic sort by (partition, key, arrival index): a key's records stay in arrival order and a
-    // partition's records are contiguous, so its demand on the region is one segmented sum
-    for (int kk = 2; kk <= SLOW_CHUNK; kk <<= 1) {
-      for (int jj = kk >> 1; jj > 0; jj >>= 1) {
-        const int o = tid ^ jj;
-        if (o > tid) {
-          const bool up = (tid & kk) == 0;
-          const int32_t pa = cp[tid], pb = cp[o];
-          const int64_t a = ck[tid], b = ck[o];
-          const int32_t ia = ci[tid], ib = ci[o];
-          const bool gt = pa > pb || (pa == pb && (a > b || (a == b && ia > ib)));
-          if (gt == up) {
-            cp[tid] = pb;
-            cp[o] = pa;
-            ck[tid] = b;
-            ck[o] = a;
-            ci[tid] = ib;
-            ci[o] = ia;
-            const int32_t da = cd[tid];
-            cd[tid] = cd[o];
-            cd[o] = da;
-          }
-        }
-        __syncthreads();
-      }
-    }
-    // capacity: every region the chunk touches must take its new windows within the load limit,
-    // and the fired-row buffer must take every row the chunk may fire; otherwise suspend here
-    if (tid < m && (tid == 0 || cp[tid - 1] != cp[tid])) {
-      int64_t demand = 0;
-      for (int j = tid; j < m && cp[j] == cp[tid]; j++) demand += cd[j];
-      const int64_t want = (int64_t)tb.live[cp[tid]] + demand;
-      if (want > region_limit(c.log_r)) {
-        bad = 1;
-        atomicMax(&st->need_live, (int32_t)min(want, (int64_t)INT32_MAX));
-      }
-    }
-    if (tid == 0) {
-      const int64_t want = (int64_t)__hip_atomic_load(&st->out_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) +
-                           (int64_t)m * row_bound;
-      if (want > out.slow_limit) {
-        bad = 1;
-        atomicMax((long long*)&st->need_out, (long long)want);
-      }
-    }
-    __syncthreads();
-    if (bad) break;
-    if (tid < m && (tid == 0 || ck[tid - 1] != ck[tid] || cp[tid - 1] != cp[tid])) {
-      for (int j = tid; j < m && ck[j] == ck[tid] && cp[j] == cp[tid]; j++) {
-        const int64_t i = b0 + ci[j];
-        const int64_t k = sk[i], t = stt[i], v = sv[i];
-        const int64_t fo = agg_ordinal(c) ? c.slow_ord[i] : 0;
-        const int32_t p = cp[j];
-        bool skipped = true;
-        if (c.assigner == FW_SESSION)
-          replay_session(x, p, k, t, v, fo, &skipped);
-        else
-          replay_time_windows(x, p, k, t, v, fo, &skipped);
-        if (skipped && jadd(t, c.lateness) <= wm) {  // isSkippedElement && isElementLate
-          if (c.side_output)
-            side_one(side, st, k, t, v);
-          else
-            late++;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (late) atomicAdd(&st->late_dropped, late);
-  if (tid == 0) {
-    atomicAdd(&st->slow_total, (unsigned long long)(min(b0, n) - first));
-    if (b0 < n) {
-      st->slow_resume = b0;
-      atomicOr(&st->suspended, (int)FW_SUSP_SLOW);
-    }
-  }
+#define FW_SLOW_CONT false
+#include "fw_slow_body.inc"
+#undef FW_SLOW_CONT
+}
+__global__ __launch_bounds__(FW_SLOW_THREADS) void k_slow_cont(DevCfg c, int64_t wm, const uint32_t* __restrict__ srow,
+                                                               int32_t T, const int64_t* __restrict__ sk,
+                                                               const int64_t* __restrict__ stt,
+                                                               const int64_t* __restrict__ sv,
+                                                               const int32_t* __restrict__ skh, DevTable tb,
+                                                               DevRows out, DevSide side, Status* st, int resume) {
+#define FW_SLOW_CONT true
+#include "fw_slow_body.inc"
+#undef FW_SLOW_CONT
 }
 
 // a fired row's block handed to the finish (out.mx for HyperLogLog, bit 63 of out.sum for t-digest) when the window
@@ -8791,6 +8748,286 @@ __global__ __launch_bounds__(256) void k_generate(uint64_t seed, int64_t first, 
   }
 }
 
+// ============================================================== ContinuousEventTimeTrigger (cont_iv())
+// .trigger(ContinuousEventTimeTrigger.of(interval)) on the aggregating operator (ContinuousEventTimeTrigger.java
+// :39-151 under WindowOperator.processElement / onEventTime, WindowOperator.java:291-469; optionally inside
+// PurgingTrigger).  An early firing copies the window's 64-byte entry into a row; no element is read again.  The
+// trigger state rides in the entry's meta (fw_cont.h), so whatever moves entries (the flush, the ordered path,
+// k_rehash, the fire kernel's rewrite) carries it.
+//
+// Arming (onElement, :58-72): the element that arms a window is the first in ARRIVAL order that finds `fire` null
+// while maxTimestamp > watermark; within a push that is the smallest batch index among the window's records.  The
+// aggregate is order-free, so arming is a pass of its own behind the push (aggregate and ordered path both done; no
+// timer runs inside a push, so arming at its end is arming at the element): k_ca<false> takes the minimum batch index
+// per unarmed entry into a per-slot word, k_ca<true> arms the entry from that record's timestamp and resets the word.
+// Both walk the push's columns by batch index (the scratch set's copies), one record per lane, and look the record's
+// windows up in the table; both skip behind a suspension and run again when the push is resumed.
+template <bool ARM>
+__global__ __launch_bounds__(256) void k_ca(DevCfg c, int64_t wm, const int64_t* __restrict__ key,
+                                            const int64_t* __restrict__ ts, const int32_t* __restrict__ kh, int64_t n,
+                                            DevTable tb, uint32_t* __restrict__ first, Status* st) {
+  if (__hip_atomic_load(&st->suspended, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;  // resumed later
+  bool wrap = false;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = key[i], t = ts[i];
+    const int32_t p = partition_of(c, k, key_hash_of(c.key_kind, k, kh, i));
+    if (p < 0) continue;
+    int64_t last = 0;
+    int nw = 0;
+    const int cls = classify<true>(c, wm, t, &last, &nw, k, 0);
+    if (cls != CLS_NORMAL && cls != CLS_SLOW) continue;  // (the push took no other record)
+    const Region r = region_of(c, tb, p, tb.cur[p]);
+    for (int wi = 0; wi < nw; wi++) {  // (nw <= DevCfg::wpr)
+      const int64_t s = jsub(last, (int64_t)wi * c.slide), e = jadd(s, c.size);
+      if (jsub(e, 1) <= wm) continue;  // onElement fired at once and armed nothing (or the window was late)
+      const int32_t slot = region_find(r, slot_hash(c, k, s), k, s, e);
+      if (slot < 0) continue;  // (cannot happen: the push stored every such window)
+      const uint32_t g = ((uint32_t)p << c.log_r) | (uint32_t)slot;
+      if constexpr (!ARM) {
+        if (!(r.ent[slot].meta & FW_CF_SET)) atomicMin(&first[g], (uint32_t)i);
+      } else {
+        if (first[g] != (uint32_t)i) continue;
+        const int64_t fire = fw_first_fire(t, cont_iv(c));
+        int64_t meta;
+        if (!fw_cf_pack(s, fire, (uint32_t)(r.ent[slot].meta & FW_TIMER) | FW_CF_REG | FW_CF_SET, &meta)) wrap = true;
+        r.ent[slot].meta = meta;
+        first[g] = 0xffffffffu;
+        if (__hip_atomic_load(&tb.next_timer[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > fire)
+          atomicMin((long long*)&tb.next_timer[p], (long long)fire);
+      }
+    }
+  }
+  if (wrap) atomicOr(&st->flags, FW_STATUS_CF_WRAP);
+}
+
+__device__ __forceinline__ uint64_t cf_entry_count(const DevCfg& c, int64_t wm, const Entry& e) {
+  return fw_cf_count(jsub(e.end, 1), cleanup_of(e.end, c.lateness), fw_cf_fire(e.meta, e.start), fw_cf_flags(e.meta),
+                     cont_iv(c), c.purging != 0, e.cnt > 0, wm);
+}
+// Counting pass of a watermark: per due region and entry the closed-form count of its firings up to
+// min(wm, cleanup) (fw_cf_count); ctr[0] += their sum, ctr[1] = the most of one window.  Writes nothing else: the
+// host grows the row buffer, or refuses the watermark, before anything changes.
+__global__ __launch_bounds__(FW_FIRE_THREADS) void k_cf_count(DevCfg c, int64_t wm, DevTable tb, unsigned long long* ctr) {
+  const int32_t p = blockIdx.x;
+  if (tb.next_timer[p] > wm) return;
+  __shared__ unsigned long long sum_s, max_s;
+  if (threadIdx.x == 0) sum_s = max_s = 0;
+  __syncthreads();
+  const Region r = region_of(c, tb, p, tb.cur[p]);
+  const uint32_t R = r.mask + 1;
+  unsigned long long sum = 0, mx = 0;
+  for (uint32_t s = threadIdx.x; s < R; s += blockDim.x) {  // (the slot count)
+    if (st_kind(ld_state_wg(r.state + s)) != SLOT_LIVE) continue;
+    const unsigned long long k = cf_entry_count(c, wm, r.ent[s]);
+    sum += k;
+    mx = max(mx, k);
+  }
+  if (sum) {
+    atomicAdd(&sum_s, sum);
+    atomicMax(&max_s, mx);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && sum_s) {
+    atomicAdd(&ctr[0], sum_s);
+    atomicMax(&ctr[1], max_s);
+  }
+}
+
+// Writing pass (HeapInternalTimerService.advanceWatermark for the region's timers <= wm, as k_fire does it: a scan
+// of the region and a rewrite of the survivors into its other buffer).  Each live entry emits its k rows (equal rows:
+// nothing arrives between two timers of one advance), takes its trigger state after those timers (fw_cf_advance), is
+// emptied by a purging firing and stays until its cleanup time, when it is dropped.  One entry per lane writes its own
+// k rows one after the other: k is advance / interval, a handful in a running job (1 to 4 on the C2-shaped stream
+// with interval 250), so a wave-cooperative row writer would spend its shuffles on loops of two or three trips; the
+// 2^20 bound (the host refuses more) is what a lane may be asked for at the worst.  The row buffer has room for every
+// row: k_cf_count's sum went through the host first.
+__global__ __launch_bounds__(FW_FIRE_THREADS) void k_cf_fire(DevCfg c, int64_t wm, DevTable tb, DevRows out, Status* st) {
+  const int32_t p = blockIdx.x;
+  if (tb.next_timer[p] > wm || __hip_atomic_load(&st->suspended, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  __shared__ int live_s;
+  __shared__ long long next_s;
+  __shared__ uint32_t sw[FW_FIRE_THREADS / 64 + 1];
+  __shared__ unsigned long long base_s;
+  const int X = tb.cur[p], Y = X ^ 1;
+  const Region rx = region_of(c, tb, p, X), ry = region_of(c, tb, p, Y);
+  const uint32_t R = rx.mask + 1;
+  for (uint32_t s = threadIdx.x; s < R; s += blockDim.x) ry.state[s] = SLOT_EMPTY;
+  if (threadIdx.x == 0) {
+    live_s = 0;
+    next_s = LMAX;
+  }
+  uint32_t nrows = 0;
+  for (uint32_t s = threadIdx.x; s < R; s += blockDim.x)
+    if (st_kind(ld_state_wg(rx.state + s)) == SLOT_LIVE) nrows += (uint32_t)cf_entry_count(c, wm, rx.ent[s]);
+  uint32_t total;
+  const uint32_t pos0 = block_excl_scan(nrows, sw, &total);
+  if (threadIdx.x == 0) base_s = total ? atomicAdd(&st->out_rows, (unsigned long long)total) : 0ull;
+  __syncthreads();  // (and the cleared state words of ry)
+  unsigned long long pos = base_s + pos0;
+  int live = 0;
+  int64_t nt = LMAX;
+  for (uint32_t s = threadIdx.x; s < R; s += blockDim.x) {
+    if (st_kind(ld_state_wg(rx.state + s)) != SLOT_LIVE) continue;
+    Entry e = rx.ent[s];
+    const int64_t M = jsub(e.end, 1), C = cleanup_of(e.end, c.lateness);
+    const uint64_t k = cf_entry_count(c, wm, e);
+    if (k) {
+      if ((int64_t)(pos + k) <= out.cap) {
+        const int64_t os = sum_out(c, e.sum), omn = mn_out(c, e.mn), omx = mx_out(c, e.mx);
+        for (uint64_t j = 0; j < k; j++) {  // (k: counted before the loop, <= 2^20)
+          const unsigned long long q = pos + j;
+          out.key[q] = e.key;
+          out.start[q] = e.start;
+          out.end[q] = e.end;
+          out.cnt[q] = e.cnt;
+          out.sum[q] = os;
+          out.mn[q] = omn;
+          out.mx[q] = omx;
+        }
+      } else {
+        atomicOr(&st->flags, FW_STATUS_OUT_FULL);  // cannot happen: the host made room for the counted rows
+      }
+      pos += k;
+    }
+    if (C != LMAX && C <= wm) continue;  // GC timer: clearAllState (WindowOperator.java:461-463), the trigger's too
+    int64_t fire = fw_cf_fire(e.meta, e.start);
+    uint32_t fl = fw_cf_flags(e.meta);
+    bool cleared;
+    fw_cf_advance(M, C, cont_iv(c), c.purging != 0, e.cnt > 0, wm, &fire, &fl, &cleared);
+    if (cleared) acc_clear(c, e);  // FIRE_AND_PURGE: the window stays, with its fire time and cleanup timer
+    fw_cf_pack(e.start, fire, fl, &e.meta);
+    const uint64_t h = slot_hash(c, e.key, e.start);
+    const int32_t dst = region_claim<true>(ry, h, live_word(h));
+    if (dst >= 0) {
+      ry.ent[dst] = e;
+      live++;
+      nt = min(nt, fw_cf_next(M, C, fire, fl));
+    } else {
+      atomicOr(&st->flags, FW_STATUS_STATE_LOST);  // cannot happen: the survivors fit the region they came from
+    }
+  }
+  if (live) atomicAdd(&live_s, live);
+  if (nt != LMAX) atomicMin(&next_s, (long long)nt);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (total) atomicAdd(&st->fired_total, (unsigned long long)total);
+    tb.cur[p] = (uint8_t)Y;
+    tb.live[p] = live_s;
+    tb.next_timer[p] = next_s;
+  }
+}
+
+// numKeyedStateEntries / numEventTimeTimers: entries with contents; maxTimestamp, fire time and cleanup time of every
+// entry, coinciding times once (HeapInternalTimerService keeps a set)
+__global__ __launch_bounds__(FW_FIRE_THREADS) void k_cf_stats(DevCfg c, DevTable tb, unsigned long long* out3) {
+  const int32_t p = blockIdx.x;
+  const Region r = region_of(c, tb, p, tb.cur[p]);
+  unsigned long long live = 0, timers = 0;
+  for (uint32_t s = threadIdx.x; s <= r.mask; s += blockDim.x) {
+    if (st_kind(ld_state(r.state + s)) != SLOT_LIVE) continue;
+    const Entry& e = r.ent[s];
+    const int64_t meta = e.meta, C = cleanup_of(e.end, c.lateness);
+    live += e.cnt > 0;
+    timers += (unsigned)fw_cf_timers(jsub(e.end, 1), C, fw_cf_fire(meta, e.start), fw_cf_flags(meta), C != LMAX);
+  }
+  if (live) atomicAdd(&out3[0], live);
+  if (timers) atomicAdd(&out3[1], timers);
+}
+
+// keyed-state snapshot with the trigger state (k_snapshot's rows plus the fire time; an emptied entry is a row too:
+// its fire time and timers are state)
+__global__ __launch_bounds__(FW_FIRE_THREADS) void k_cf_snapshot(DevCfg c, DevTable tb, int32_t p0, StateCols out,
+                                                                int64_t* __restrict__ fire, unsigned long long* count) {
+  __shared__ uint32_t sw[FW_FIRE_THREADS / 64 + 1];
+  __shared__ unsigned long long base_s;
+  const int32_t p = p0 + blockIdx.x;
+  const Region r = region_of(c, tb, p, tb.cur[p]);
+  const uint32_t R = r.mask + 1;
+  for (uint32_t s0 = 0; s0 < R; s0 += blockDim.x) {
+    const uint32_t s = s0 + threadIdx.x;
+    const bool live = s < R && st_kind(ld_state(r.state + s)) == SLOT_LIVE;
+    uint32_t total;
+    const uint32_t pos = block_excl_scan(live ? 1u : 0u, sw, &total);
+    if (threadIdx.x == 0) base_s = total ? atomicAdd(count, (unsigned long long)total) : 0ull;
+    __syncthreads();
+    if (live) {
+      const Entry e = r.ent[s];
+      const unsigned long long o = base_s + pos;
+      out.key[o] = e.key;
+      out.start[o] = e.start;
+      out.end[o] = e.end;
+      out.cnt[o] = e.cnt;
+      out.sum[o] = sum_out(c, e.sum);
+      out.mn[o] = mn_out(c, e.mn);
+      out.mx[o] = mx_out(c, e.mx);
+      out.timer[o] = e.meta & (FW_CF_MTIMER | FW_CF_REG);
+      fire[o] = (e.meta & FW_CF_SET) ? fw_cf_fire(e.meta, e.start) : LMIN;
+    }
+    __syncthreads();
+  }
+}
+
+// restore of such rows (k_restore with the trigger state).  A row whose (key, window) is already present merges:
+// the accumulators by AggregateFunction.merge, the fire time by Min as the trigger's ReducingState does, the timers
+// of the surviving fire time
+__global__ void k_cf_restore(DevCfg c, int32_t kg, StateCols in, const int64_t* __restrict__ fire, int64_t n,
+                             DevTable tb, Status* st, const int32_t* round_of, int32_t round) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || (round_of && round_of[i] != round)) return;
+  const int32_t p = restore_partition(c, kg, in.key[i]);
+  if (p < 0) return;
+  Entry d;
+  d.key = in.key[i];
+  d.start = in.start[i];
+  d.end = in.end[i];
+  d.cnt = in.cnt[i];
+  d.sum = in.sum[i];
+  d.mn = c.vtype == FW_VAL_F64 ? f64_sortable(in.mn[i]) : in.mn[i];
+  d.mx = c.vtype == FW_VAL_F64 ? f64_sortable(in.mx[i]) : in.mx[i];
+  if (d.cnt == 0) acc_clear(c, d);
+  int64_t df = fire[i];
+  uint32_t dfl = (uint32_t)in.timer[i] & (FW_CF_MTIMER | FW_CF_REG);
+  if (df != LMIN) {
+    dfl |= FW_CF_SET;
+  } else {  // null: no timer behind it
+    dfl &= ~FW_CF_REG;
+    df = d.start;
+  }
+  const int64_t M = jsub(d.end, 1), C = cleanup_of(d.end, c.lateness);
+  const Region r = region_of(c, tb, p, tb.cur[p]);
+  const uint64_t h = slot_hash(c, d.key, d.start);
+  const int32_t found = region_find(r, h, d.key, d.start, d.end);
+  if (found >= 0) {
+    Entry cur = r.ent[found];
+    acc_merge(c, cur, d);
+    int64_t cf = fw_cf_fire(cur.meta, cur.start);
+    uint32_t cfl = fw_cf_flags(cur.meta);
+    const uint32_t mt = (cfl | dfl) & FW_CF_MTIMER;
+    if ((dfl & FW_CF_SET) && (!(cfl & FW_CF_SET) || df < cf)) {
+      cf = df;
+      cfl = dfl;
+    } else if ((dfl & FW_CF_SET) && df == cf) {
+      cfl |= dfl;
+    }
+    cfl = (cfl & ~FW_CF_MTIMER) | mt;
+    if (!fw_cf_pack(cur.start, cf, cfl, &cur.meta)) atomicOr(&st->flags, FW_STATUS_CF_WRAP);
+    r.ent[found] = cur;
+    atomicMin((long long*)&tb.next_timer[p], (long long)fw_cf_next(M, C, cf, cfl));
+    return;
+  }
+  if (!fw_cf_pack(d.start, df, dfl, &d.meta)) atomicOr(&st->flags, FW_STATUS_CF_WRAP);
+  const int32_t s = region_claim(r, h, SLOT_BUSY);
+  if (s < 0) {
+    atomicOr(&st->flags, FW_STATUS_STATE_LOST);
+    return;
+  }
+  r.ent[s] = d;
+  __threadfence();
+  __hip_atomic_store(r.state + s, live_word(h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  atomicAdd(&tb.live[p], 1);
+  atomicMin((long long*)&tb.next_timer[p], (long long)fw_cf_next(M, C, df, dfl));
+}
+
 }  // namespace
 
 // ============================================================================== launchers
@@ -8819,6 +9056,9 @@ void launch_classify_hist(const DevCfg& c, int64_t wm, const int64_t* key, const
       break;
     case M_PANE:
       hipLaunchKernelGGL(k_classify_hist<M_PANE>, dim3(T), dim3(FW_TILE_THREADS), lds, s, c, wm, key, ts, kh, n, T, hist, st, rsv);
+      break;
+    case M_CONT:
+      hipLaunchKernelGGL(k_classify_hist<M_CONT>, dim3(T), dim3(FW_TILE_THREADS), lds, s, c, wm, key, ts, kh, n, T, hist, st, rsv);
       break;
     default:
       hipLaunchKernelGGL(k_classify_hist<M_GEN>, dim3(T), dim3(FW_TILE_THREADS), lds, s, c, wm, key, ts, kh, n, T, hist, st, rsv);
@@ -8909,11 +9149,18 @@ void launch_scatter(const DevCfg& c, int64_t wm, const int64_t* key, const int64
       hipLaunchKernelGGL(k_scatter<M_PANE>, dim3(T), dim3(FW_TILE_THREADS), lds, s, c, wm, key, ts, val, kh, n, T, o, part,
                          side, st);
       break;
+    case M_CONT:
+      hipLaunchKernelGGL(k_scatter<M_CONT>, dim3(T), dim3(FW_TILE_THREADS), lds, s, c, wm, key, ts, val, kh, n, T, o, part,
+                         side, st);
+      break;
     default:
       hipLaunchKernelGGL(k_scatter<M_GEN>, dim3(T), dim3(FW_TILE_THREADS), lds, s, c, wm, key, ts, val, kh, n, T, o, part,
                          side, st);
   }
-  if (!c.dense)  // (dense configurations never have a record that needs arrival order)
+  if (cont_iv(c))
+    hipLaunchKernelGGL(k_scatter_ordered_cont, dim3(T), dim3(FW_TILE_THREADS), 0, s, c, wm, key, ts, val, kh, n, T,
+                       (const uint32_t*)(offs + (int64_t)c.P * T), sk, stt, sv, skh, (const Status*)st);
+  else if (!c.dense)  // (dense configurations never have a record that needs arrival order)
     hipLaunchKernelGGL(k_scatter_ordered, dim3(T), dim3(FW_TILE_THREADS), 0, s, c, wm, key, ts, val, kh, n, T,
                        (const uint32_t*)(offs + (int64_t)c.P * T), sk, stt, sv, skh, (const Status*)st);
 }
@@ -9052,8 +9299,39 @@ void launch_row_update(const DevCfg& c, const PRec* part, const uint32_t* offs, 
 void launch_slow(const DevCfg& c, int64_t wm, const uint32_t* srow, int32_t T, const int64_t* sk, const int64_t* stt,
                  const int64_t* sv, const int32_t* skh, DevTable tb, DevRows out, DevSide side, Status* st, int resume,
                  hipStream_t s) {
-  hipLaunchKernelGGL(k_slow, dim3(1), dim3(FW_SLOW_THREADS), 0, s, c, wm, srow, T, sk, stt, sv, skh, tb, out, side,
-                     st, resume);
+  if (cont_iv(c))
+    hipLaunchKernelGGL(k_slow_cont, dim3(1), dim3(FW_SLOW_THREADS), 0, s, c, wm, srow, T, sk, stt, sv, skh, tb, out,
+                       side, st, resume);
+  else
+    hipLaunchKernelGGL(k_slow, dim3(1), dim3(FW_SLOW_THREADS), 0, s, c, wm, srow, T, sk, stt, sv, skh, tb, out, side,
+                       st, resume);
+}
+
+void launch_cont_arm(const DevCfg& c, int64_t wm, const int64_t* key, const int64_t* ts, const int32_t* kh, int64_t n,
+                     DevTable tb, uint32_t* first, Status* st, hipStream_t s) {
+  if (n <= 0) return;
+  const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 8192));
+  hipLaunchKernelGGL(k_ca<false>, grid, dim3(256), 0, s, c, wm, key, ts, kh, n, tb, first, st);
+  hipLaunchKernelGGL(k_ca<true>, grid, dim3(256), 0, s, c, wm, key, ts, kh, n, tb, first, st);
+}
+void launch_cont_count(const DevCfg& c, int64_t wm, DevTable tb, unsigned long long* ctr, hipStream_t s) {
+  hipLaunchKernelGGL(k_cf_count, dim3(c.P), dim3(FW_FIRE_THREADS), 0, s, c, wm, tb, ctr);
+}
+void launch_cont_fire(const DevCfg& c, int64_t wm, DevTable tb, DevRows out, Status* st, hipStream_t s) {
+  FW_LAUNCH_MAIN(k_cf_fire, dim3(c.P), dim3(FW_FIRE_THREADS), 0, s, c, wm, tb, out, st);
+}
+void launch_cont_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t s) {
+  hipLaunchKernelGGL(k_cf_stats, dim3(c.P), dim3(FW_FIRE_THREADS), 0, s, c, tb, out3);
+}
+void launch_cont_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, StateCols out, int64_t* fire,
+                          unsigned long long* count, hipStream_t s) {
+  hipLaunchKernelGGL(k_cf_snapshot, dim3(np), dim3(FW_FIRE_THREADS), 0, s, c, tb, p0, out, fire, count);
+}
+void launch_cont_restore(const DevCfg& c, int32_t kg, StateCols in, const int64_t* fire, int64_t n, DevTable tb,
+                         Status* st, const int32_t* round_of, int32_t rounds, hipStream_t s) {
+  const dim3 grid((unsigned)((n + 255) / 256));
+  for (int32_t r = 0; r < rounds; r++)
+    hipLaunchKernelGGL(k_cf_restore, grid, dim3(256), 0, s, c, kg, in, fire, n, tb, st, round_of, r);
 }
 
 void launch_fire(const DevCfg& c0, int64_t wm, DevTable tb, DevRows out, Status* st, hipStream_t s) {

@@ -105,6 +105,9 @@ struct DevCfg {
   int32_t assigner, vtype, key_kind, purging;
   int32_t side_output, max_par, kg0, n_kg;
   int32_t log_s, P, log_r, wpr;  // wpr = max windows per record: sliding ceil(size / slide) + 1 (a displaced record's extra window; panes refuse those: + 0)
+  // gap: the session gap.  Tumbling / sliding handles (sessions are refused there) carry the interval of
+  // ContinuousEventTimeTrigger.of(interval) in it, 0 = EventTimeTrigger: cont_iv() below.  (No field of its own: a
+  // kernel that keeps its DevCfg copy in scratch would grow by it.)
   int64_t size, slide, offset, gap, lateness;
   int32_t diag;                  // FW_DIAG ablation bits (diagnostic builds of the timing only; 0 in production)
   // the field's width (FW_VAL_I16 / I8 / F32 are kept as I32 / F64 inside): sums wrap to sum_bits (64, 32, 16
@@ -205,6 +208,10 @@ struct DevCfg {
   const uint8_t* row_nulls;
   int64_t row_stride;
 };
+// ContinuousEventTimeTrigger on the aggregating operator (fw_config::trigger; fw_cont.h): its interval, 0 = the handle
+// runs EventTimeTrigger.  Such a handle keeps windows (no panes, dense regions, compact records or single pass) and
+// runs the _cont instantiations and the k_ca / k_cf_* kernels.
+__host__ __device__ inline int64_t cont_iv(const DevCfg& c) { return c.assigner == 2 /* FW_SESSION */ ? 0 : c.gap; }
 // FW_AGG_ROW accumulator of one column (40 bytes, zero = empty): the non-null count, the sum (integral columns: 128
 // bits, two's complement, lo / hi; floating columns: f64 in lo), min / max as order keys encoded so that 0 is the
 // identity of an unsigned max (row_enc_min / row_enc_max)
@@ -296,7 +303,9 @@ enum {
   FW_STATUS_SIDE_FULL = 8,
   FW_STATUS_POOL = 16,       // the accumulator block pool (HyperLogLog registers, t-digests) ran out of blocks
   FW_STATUS_TD_UNION = 32,   // a late session firing joined more centroids than its union scratch holds
-  FW_STATUS_ABOVE_WINDOW = 64  // a tumbling record at or above its window's end was taken (no error: fw_combine_extract refuses)
+  FW_STATUS_ABOVE_WINDOW = 64,  // a tumbling record at or above its window's end was taken (no error: fw_combine_extract refuses)
+  FW_STATUS_CF_WRAP = 128  // ContinuousEventTimeTrigger: a window that wraps around the long range was armed (its fire
+                           // time does not fit the entry, fw_cont.h): FW_ERR_TIME_RANGE
 };
 // a region takes new windows only up to this load; beyond it the kernel suspends and the table grows
 __host__ __device__ inline int32_t region_limit(int32_t log_r) { return (int32_t)((3ll << log_r) >> 2); }
@@ -514,6 +523,24 @@ void launch_slow(const DevCfg& c, int64_t wm, const uint32_t* srow, int32_t T, c
                  const int64_t* stt, const int64_t* sv, const int32_t* skh, DevTable tb, DevRows out, DevSide side,
                  Status* st, int resume, hipStream_t_ s);
 void launch_fire(const DevCfg& c, int64_t wm, DevTable tb, DevRows out, Status* st, hipStream_t_ s);
+// ---- ContinuousEventTimeTrigger (cont_iv(); fw_cont.h)
+// arming, behind a push's aggregate and ordered path (both skip behind a suspension and run again when the push is
+// resumed): key / ts / kh = the push's columns by batch index (the scratch set's copies), first = one word per table
+// slot, all ones between pushes
+void launch_cont_arm(const DevCfg& c, int64_t wm, const int64_t* key, const int64_t* ts, const int32_t* kh, int64_t n,
+                     DevTable tb, uint32_t* first, Status* st, hipStream_t_ s);
+// counting pass of a watermark: ctr[0] += the rows it fires, ctr[1] = max over the windows (zeroed by the caller);
+// writes nothing else
+void launch_cont_count(const DevCfg& c, int64_t wm, DevTable tb, unsigned long long* ctr, hipStream_t_ s);
+// writing pass: the rows, the entries' trigger state, purge / cleanup, survivors into the other buffer, next_timer
+void launch_cont_fire(const DevCfg& c, int64_t wm, DevTable tb, DevRows out, Status* st, hipStream_t_ s);
+void launch_cont_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t_ s);
+// snapshot / restore with the trigger state: fire = the fire time per row (Long.MIN_VALUE = null), the timer column's
+// bit 0 = maxTimestamp's timer, bit 1 = the timer at the fire time
+void launch_cont_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, StateCols out, int64_t* fire,
+                          unsigned long long* count, hipStream_t_ s);
+void launch_cont_restore(const DevCfg& c, int32_t kg, StateCols in, const int64_t* fire, int64_t n, DevTable tb,
+                         Status* st, const int32_t* round_of, int32_t rounds, hipStream_t_ s);
 int64_t pane_nt_floor(const DevCfg& c, int64_t wm);  // host: DevCfg::nt_floor of a launch at watermark wm
 // FW_AGG_HLL: fold the batch's records into the registers of their (key, window) entries (after aggregate)
 void launch_hll_update(const DevCfg& c, const PRec* part, const uint32_t* offs, int32_t T, int64_t n, DevTable tb,

@@ -61,6 +61,16 @@ FW_RANGE_HD inline bool fw_sliding_runaway(int64_t size, int64_t slide, int64_t 
   }
   return s > lo;
 }
+// ContinuousEventTimeTrigger.onElement's first fire time of a window, from the element that finds the trigger's
+// "fire-time" state null: start = timestamp - (timestamp % interval), nextFireTimestamp = start + interval
+// (ContinuousEventTimeTrigger.java:64-65; Java's truncating %, wrapping longs; iv > 0)
+FW_RANGE_HD inline int64_t fw_first_fire(int64_t ts, int64_t iv) { return fw_wadd(fw_wsub(ts, ts % iv), iv); }
+// The aggregating operator under ContinuousEventTimeTrigger refuses a record with ts > Long.MAX_VALUE - interval: its
+// first fire time, or the timer the trigger registers after that one (fire + interval), wraps past Long.MAX_VALUE,
+// and the chain of early firings would go on from the bottom of the long range (DESIGN.md "Event-time arithmetic",
+// excluded class (2))
+FW_RANGE_HD inline bool fw_first_fire_wraps(int64_t ts, int64_t iv) { return ts > INT64_MAX - iv; }
+
 // compact records: window deltas count from 2^(log_s - 1) windows (or panes) before the watermark's, so a batch's
 // windows on both sides of the watermark fit; false: no base (it leaves the long range near Long.MIN_VALUE)
 inline bool fw_compact_base(int64_t wm, int64_t offset, int64_t slide, int log_s, int64_t* base) {

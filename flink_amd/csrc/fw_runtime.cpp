@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/flink_window.h"
+#include "fw_cont.h"
 #include "fw_internal.h"
 #include "fw_range.h"
 
@@ -48,6 +49,10 @@ struct Scratch {
   int64_t* byv = nullptr;        // FW_AGG_MINBY / MAXBY: the batch's value column (DevCfg::by_val)
   int64_t* rowc = nullptr;       // FW_AGG_ROW: the batch's value columns (column j at j * max_batch), DevCfg::row_cols
   uint8_t* rown = nullptr;       //             and NULL masks (DevCfg::row_nulls)
+  // ContinuousEventTimeTrigger: the batch's key, timestamp and key-hash columns by batch index, for the arming pass
+  // behind the push (fwdev::launch_cont_arm), possibly after the caller's columns are gone (a resumed push)
+  int64_t *ck = nullptr, *ct = nullptr;
+  int32_t* ckh = nullptr;
   int32_t T = 0;                 // tiles of the batch that used this set
   int64_t n = 0;                 // records of the batch
   bool split = false;            // its aggregate split long partitions (fw_op::hot)
@@ -126,6 +131,10 @@ struct fw_op {
   int64_t dig_stride = 0;    // words per row of DevRows::dig (t-digest export: 1 + delta; FW_AGG_ROW: 1 + aggregates)
   int64_t* iota = nullptr;   // FW_AGG_ROW: 0, 1, ... (a record's value is its index in the push)
   int32_t* d_disp = nullptr;  // panes: the displaced-record check's flag (refuse_displaced)
+  // ContinuousEventTimeTrigger (cont_iv(dc)): the arming pass's word per table slot (all ones between pushes; follows
+  // the table when it grows) and the counting pass's two counters.  Allocated for such handles only.
+  uint32_t* cf_first = nullptr;
+  unsigned long long* cf_ctr = nullptr;
   uint32_t range_seen = 0;     // Status::range_errors as last settled (the device only adds to it)
   int64_t range_pending = 0;   // refused device-column records not yet reported (settle)
 
@@ -244,6 +253,11 @@ int alloc_scratch(fw_op* op, Scratch& s, int64_t mb, int64_t m) {
     HIP_OR_RETURN(op, dmalloc(&s.rowc, (size_t)(mb * op->dc.row_nc)));
     HIP_OR_RETURN(op, dmalloc(&s.rown, (size_t)mb));
   }
+  if (cont_iv(op->dc)) {
+    HIP_OR_RETURN(op, dmalloc(&s.ck, mb));
+    HIP_OR_RETURN(op, dmalloc(&s.ct, mb));
+    if (op->cfg.key_kind == FW_KEY_HASHED) HIP_OR_RETURN(op, dmalloc(&s.ckh, mb));
+  }
   return FW_OK;
 }
 void free_scratch(Scratch& s) {
@@ -261,6 +275,9 @@ void free_scratch(Scratch& s) {
   dfree(s.pparts);
   dfree(s.so);
   dfree(s.byv);
+  dfree(s.ck);
+  dfree(s.ct);
+  dfree(s.ckh);
 }
 
 // buffers of the split-partition aggregate (AggHot): deltas at record indices, so one Entry per record
@@ -494,6 +511,12 @@ int grow_table(fw_op* op, int new_log_r) {
   op->table_slots = (int64_t)nc.P << nc.log_r;
   op->grows++;
   if (op->dc.agg == FW_AGG_ROW && (rc = grow_pool(op, row_pool_blocks(op->dc)))) return rc;
+  if (op->cf_first) {  // (all ones between a push's two arming kernels' launches and always between pushes)
+    if (op->table_slots >= (int64_t(1) << 32)) return set_err(op, FW_ERR_CAPACITY, "state table would exceed 2^32 slots");
+    dfree(op->cf_first);
+    HIP_OR_RETURN(op, dmalloc(&op->cf_first, (size_t)op->table_slots));
+    HIP_OR_RETURN(op, hipMemsetAsync(op->cf_first, 0xff, (size_t)op->table_slots * sizeof(uint32_t), op->stream));
+  }
   if (op->dc.agg == FW_AGG_TDIGEST) {  // the compression's per-slot index follows the table
     if (op->table_slots >= (int64_t(1) << 31)) return set_err(op, FW_ERR_CAPACITY, "t-digest table would exceed 2^31 slots");
     dfree(op->td.lidx);
@@ -617,6 +640,10 @@ int settle_quiet(fw_op* op) {
       fwdev::launch_slow(c, S.wm, S.hist + (int64_t)op->dc.P * S.T, S.T, S.sk, S.stt, S.sv, S.skh, op->tb, op->out,
                          op->side, op->d_status, (susp & FW_SUSP_AGG) ? 0 : 1, op->stream);
     });
+    // ContinuousEventTimeTrigger: the arming pass skipped itself behind the suspension (it runs once, on the
+    // completed push; behind another suspension it skips itself again)
+    if (op->cf_first)
+      fwdev::launch_cont_arm(c, S.wm, S.ck, S.ct, S.ckh, S.n, op->tb, op->cf_first, op->d_status, op->stream);
     // the t-digest compression skipped itself behind the suspension (it runs once, after the aggregate and the
     // ordered path completed)
     if ((susp & (FW_SUSP_AGG | FW_SUSP_SLOW)) && c.agg == FW_AGG_TDIGEST)
@@ -674,6 +701,10 @@ int settle_quiet(fw_op* op) {
     return set_err(op, FW_ERR_CAPACITY, "accumulator block pool exhausted (%lld blocks; raise expected_entries)",
                    (long long)op->dc.pool_blocks);
   if (s.flags & FW_STATUS_SIDE_FULL) return set_err(op, FW_ERR_STATE, "side-output buffer overflow");
+  if (s.flags & FW_STATUS_CF_WRAP)
+    return set_err(op, FW_ERR_TIME_RANGE,
+                   "ContinuousEventTimeTrigger: a window that wraps around the long range was armed; its fire time is "
+                   "not kept (timestamps within size + slide of an end of the range)");
   if (s.kg_errors) return set_err(op, FW_ERR_KEY_GROUP, "%d record(s) outside KeyGroupRange [%d, %d]", s.kg_errors,
                                    op->dc.kg0, op->dc.kg0 + op->dc.n_kg - 1);
   if (s.ts_errors)
@@ -757,7 +788,11 @@ int time_range_error(fw_op* op, int64_t bad) {
   return set_err(op, FW_ERR_TIME_RANGE,
                  "%lld record(s) with a timestamp at an end of the long range that this operator does not take: %s",
                  (long long)bad,
-                 op->dc.panes ? "sliding windows kept as panes refuse a record whose window end wraps past "
+                 cont_iv(op->dc) ? "under ContinuousEventTimeTrigger a record with ts > Long.MAX_VALUE - interval is "
+                                   "refused (its first fire time ts - ts % interval + interval, or the timer after "
+                                   "it, wraps: the early firings would go on from the bottom of the range), and so is what the reference's own sliding assigner "
+                                   "does not return on"
+                 : op->dc.panes ? "sliding windows kept as panes refuse a record whose window end wraps past "
                                 "Long.MAX_VALUE or that lies within size + 2 slide of Long.MIN_VALUE (create the "
                                 "operator with no_panes for such timestamps)"
                               : "the reference's own sliding assigner does not return on a timestamp just above "
@@ -766,12 +801,16 @@ int time_range_error(fw_op* op, int64_t bad) {
 }
 int refuse_time_range_host(fw_op* op, const int64_t* ts, int64_t n) {
   const DevCfg& c = op->dc;
-  if (op->cfg.assigner != FW_SLIDING) return FW_OK;
+  int64_t bad = 0;
+  if (const int64_t iv = cont_iv(c)) {  // ContinuousEventTimeTrigger: the first fire time wraps (classify<true>)
+    for (int64_t i = 0; i < n; i++) bad += fw_first_fire_wraps(ts[i], iv);
+  }
+  if (op->cfg.assigner != FW_SLIDING) return bad ? time_range_error(op, bad) : FW_OK;
   int64_t lo, hi;  // only a timestamp within size + 2 slide of an end can be one
   fw_range_guards(c.size, c.slide, &lo, &hi);
-  int64_t bad = 0;
   for (int64_t i = 0; i < n; i++)
-    if ((ts[i] <= lo || ts[i] >= hi) && ts[i] != INT64_MIN) bad += time_range_record(c, ts[i]);
+    if ((ts[i] <= lo || ts[i] >= hi) && ts[i] != INT64_MIN && !(cont_iv(c) && fw_first_fire_wraps(ts[i], cont_iv(c))))
+      bad += time_range_record(c, ts[i]);
   return bad ? time_range_error(op, bad) : FW_OK;
 }
 // ---- displaced records (DESIGN.md "Event-time arithmetic"): ts - offset + slide < 0 off the slide grid.  The reference
@@ -915,6 +954,12 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
   // minBy / maxBy: the aggregate reads the selected elements' fields back by batch index, possibly after the
   // caller's columns are gone (a resumed push), so the batch keeps its own copy
   if (S.byv) HIP_OR_RETURN(op, hipMemcpyAsync(S.byv, val, n * sizeof(int64_t), hipMemcpyDeviceToDevice, bs));
+  // ContinuousEventTimeTrigger: the arming pass reads the batch's keys and timestamps by batch index, likewise
+  if (S.ck) {
+    HIP_OR_RETURN(op, hipMemcpyAsync(S.ck, key, n * sizeof(int64_t), hipMemcpyDeviceToDevice, bs));
+    HIP_OR_RETURN(op, hipMemcpyAsync(S.ct, ts, n * sizeof(int64_t), hipMemcpyDeviceToDevice, bs));
+    if (S.ckh) HIP_OR_RETURN(op, hipMemcpyAsync(S.ckh, kh, n * sizeof(int32_t), hipMemcpyDeviceToDevice, bs));
+  }
   HIP_OR_RETURN(op, hipGetLastError());
   if (two) {  // the batch's aggregate waits for its scatter
     HIP_OR_RETURN(op, hipEventRecord(op->ev_scat[nxt], bs));
@@ -980,6 +1025,10 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
       fwdev::launch_slow(cc, op->wm, S.hist + (int64_t)cc.P * S.T, S.T, S.sk, S.stt, S.sv, S.skh, op->tb, op->out,
                          op->side, op->d_status, 0, op->stream);
     });
+  // ContinuousEventTimeTrigger: the push's windows without a fire time are armed from their first element in arrival
+  // order, behind the aggregate and the ordered path (behind a suspension the pass skips itself: settle)
+  if (op->cf_first)
+    fwdev::launch_cont_arm(cc, op->wm, S.ck, S.ct, S.ckh, n, op->tb, op->cf_first, op->d_status, op->stream);
   // the t-digest compression closes the push: after the ordered path too (sessions: its merges and added values)
   if (cc.agg == FW_AGG_TDIGEST)
     timed(op, K_TDIGEST, [&] {
@@ -1011,10 +1060,17 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
 // pane's); the combiner is a pane operator whose watermark never moves, so it refuses every push that holds one
 // (refuse_displaced_*), and a pane's start, being on the grid, is never displaced itself.
 bool combine_eligible(const fw_config& c) {
+  if (c.trigger != FW_TRIGGER_EVENT_TIME) return false;  // (a combiner's partials carry no arrival order)
   const bool panes = c.assigner == FW_SLIDING && c.slide > 0 && c.size > c.slide && c.size % c.slide == 0 && !c.no_panes &&
                      !(getenv("FW_NO_PANES") && atoi(getenv("FW_NO_PANES")));
   return (c.assigner == FW_TUMBLING || panes) && c.aggregate == FW_AGG_COUNT_SUM_MIN_MAX &&
          c.allowed_lateness == 0 && !c.side_output && (c.key_kind == FW_KEY_LONG || c.key_kind == FW_KEY_INT);
+}
+int combine_refuses_continuous(fw_op* op) {
+  return set_err(op, FW_ERR_UNSUPPORTED,
+                 "a ContinuousEventTimeTrigger handle takes no part in pre-shuffle combining: the trigger arms a window "
+                 "from its first element in arrival order, and a combiner's partials carry no arrival order (push the "
+                 "records themselves, fw_keyby_push_device)");
 }
 // HyperLogLog partials (register lists): tumbling windows, no allowed lateness, Long or Integer keys
 bool combine_eligible_hll(const fw_config& c) {
@@ -1194,6 +1250,38 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
                                   : "this aggregate takes at most 65535 windows per element");
     unsupported = true;
   }
+  // the trigger argument (WindowedStream.trigger): EventTimeTrigger, or ContinuousEventTimeTrigger.of(interval) for
+  // count/sum/min/max over tumbling and sliding windows (flink_window.h "ContinuousEventTimeTrigger on the aggregating
+  // operator"); every refusal names where the job runs instead
+  const bool continuous = cfg.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME;
+  if (!msg[0] && cfg.trigger != FW_TRIGGER_EVENT_TIME && !continuous)
+    snprintf(msg, sizeof msg, "unknown trigger %d (FW_TRIGGER_EVENT_TIME or FW_TRIGGER_CONTINUOUS_EVENT_TIME; "
+                              "CountTrigger runs on the window-contents operator, fw_list_create)", cfg.trigger);
+  if (!msg[0] && continuous) {
+    // (this reference's ContinuousEventTimeTrigger.of has no checkArgument of its own: an interval of 0 throws
+    // ArithmeticException at the first element's timestamp % interval, a negative one registers timers backwards)
+    if (cfg.trigger_interval <= 0) {
+      snprintf(msg, sizeof msg, "ContinuousEventTimeTrigger interval must be > 0");
+    } else if (cfg.assigner == FW_SESSION) {
+      snprintf(msg, sizeof msg, "ContinuousEventTimeTrigger over session windows is not offered on the aggregating "
+                                "operator (a merged session's fire time is the minimum over its founders in arrival "
+                                "order): the window-contents operator takes it (fw_list_create, GpuListWindowOperator)");
+      unsupported = true;
+    } else if (cfg.assigner == FW_COUNT) {
+      snprintf(msg, sizeof msg, "ContinuousEventTimeTrigger over count windows is not offered (GlobalWindows with "
+                                "this trigger run on the window-contents operator, fw_list_create)");
+      unsupported = true;
+    } else if (cfg.aggregate != FW_AGG_COUNT_SUM_MIN_MAX) {
+      snprintf(msg, sizeof msg, "ContinuousEventTimeTrigger is offered for the count/sum/min/max aggregate "
+                                "(FW_AGG_COUNT_SUM_MIN_MAX); aggregate %d under this trigger runs on the "
+                                "window-contents operator (fw_list_create, GpuListWindowOperator)", cfg.aggregate);
+      unsupported = true;
+    } else if ((__int128)cfg.size + cfg.allowed_lateness + 2 * (__int128)cfg.trigger_interval > (__int128)FW_CF_MAX_SPAN) {
+      snprintf(msg, sizeof msg, "ContinuousEventTimeTrigger: size + allowed lateness + 2 * interval may not exceed 2^60 "
+                                "(the window-contents operator, fw_list_create, has no such bound)");
+      unsupported = true;
+    }
+  }
   fw_op* op = new fw_op();
   op->cfg = cfg;
   if (msg[0]) {
@@ -1228,8 +1316,8 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
   // and not for a handful of keys: a dense region's run is one workgroup's, so a few hot keys would serialise the
   // batch (C1, 170 words: k_dt_aggregate 2.4 ms per step against 0.45 ms for k_aggregate's split partitions)
   c.dense = cfg.assigner == FW_TUMBLING && cfg.aggregate == FW_AGG_COUNT_SUM_MIN_MAX && cfg.allowed_lateness == 0 &&
-            (cfg.expected_entries == 0 || cfg.expected_entries >= 65536) &&
-            !(getenv("FW_NO_DENSE") && atoi(getenv("FW_NO_DENSE")));
+            (cfg.expected_entries == 0 || cfg.expected_entries >= 65536) && !continuous &&  // (arming needs arrival
+            !(getenv("FW_NO_DENSE") && atoi(getenv("FW_NO_DENSE")));                       // order: windows, PRec)
   int64_t s = cfg.sub_partitions;
   if (s == 0 && c.dense) {
     // about 3/4 of k_dt_aggregate's LDS table of live entries per region (C2: 2M live entries -> 1024 regions), at
@@ -1255,7 +1343,8 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
   c.size = cfg.size;
   c.slide = cfg.assigner == FW_SLIDING ? cfg.slide : cfg.size;
   c.offset = cfg.offset;
-  c.gap = cfg.gap;
+  // (tumbling / sliding: the slot carries ContinuousEventTimeTrigger's interval, cont_iv())
+  c.gap = cfg.assigner == FW_SESSION ? cfg.gap : continuous ? cfg.trigger_interval : 0;
   c.lateness = cfg.allowed_lateness;
   // FW_DIAG: ablation bits for pricing kernel stages in diagnostic runs only (results are wrong)
   if (const char* d = getenv("FW_DIAG")) c.diag = atoi(d);
@@ -1264,7 +1353,7 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
   // disables it)
   c.panes = cfg.assigner == FW_SLIDING && cfg.allowed_lateness == 0 && cfg.size > cfg.slide &&
             cfg.size % cfg.slide == 0 && cfg.aggregate != FW_AGG_HLL &&  // (HLL, t-digest, rows: a block per window)
-            cfg.aggregate != FW_AGG_TDIGEST && cfg.aggregate != FW_AGG_ROW && !cfg.no_panes &&
+            cfg.aggregate != FW_AGG_TDIGEST && cfg.aggregate != FW_AGG_ROW && !cfg.no_panes && !continuous &&
             !(getenv("FW_NO_PANES") && atoi(getenv("FW_NO_PANES")));
   // windows per record, at most: ceil(size / slide), and one more for a displaced record (ts - offset + slide < 0
   // off the slide grid: Java's truncating % puts its "last start" on the grid point above ts, and
@@ -1280,7 +1369,7 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
   // and at least 2 bits of sub-partition to carry the window delta (FW_NO_COMPACT=1 disables them)
   c.compact = (cfg.assigner == FW_TUMBLING || c.panes) &&
               (cfg.aggregate == FW_AGG_COUNT_SUM_MIN_MAX || cfg.aggregate == FW_AGG_HLL ||
-               cfg.aggregate == FW_AGG_TDIGEST || cfg.aggregate == FW_AGG_ROW) && c.log_s >= 2 &&
+               cfg.aggregate == FW_AGG_TDIGEST || cfg.aggregate == FW_AGG_ROW) && c.log_s >= 2 && !continuous &&
               !(getenv("FW_NO_COMPACT") && atoi(getenv("FW_NO_COMPACT")));
   const int64_t expected = cfg.expected_entries > 0 ? cfg.expected_entries : (int64_t)c.P * 512;
   if (cfg.aggregate >= FW_AGG_FIRST) c.agg = cfg.aggregate;  // (FW_AGG_HLL is set below)
@@ -1366,6 +1455,12 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
     HIP_OR_RETURN(op, hipMemcpy(op->iota, h.data(), (size_t)mb * sizeof(int64_t), hipMemcpyHostToDevice));
   }
   if (c.panes) HIP_OR_RETURN(op, dmalloc(&op->d_disp, 1));
+  if (continuous) {  // the arming pass's word per slot, the counting pass's counters (no other handle has them)
+    if (op->table_slots >= (int64_t(1) << 32)) return set_err(op, FW_ERR_CAPACITY, "state table would exceed 2^32 slots");
+    HIP_OR_RETURN(op, dmalloc(&op->cf_first, (size_t)op->table_slots));
+    HIP_OR_RETURN(op, hipMemsetAsync(op->cf_first, 0xff, (size_t)op->table_slots * sizeof(uint32_t), op->stream));
+    HIP_OR_RETURN(op, dmalloc(&op->cf_ctr, 2));
+  }
   c.wide = op->sc[0].wide;  // (every push sets its own set's word)
   // single-pass scatter: a partition's run may take twice its share of the largest batch (part holds mb PRecs
   // = 2 mb compact records), whole 128-byte lines apart
@@ -1600,6 +1695,8 @@ void fw_destroy(fw_op* op) {
   dfree(op->hoff_tmp);
   dfree(op->iota);
   dfree(op->d_disp);
+  dfree(op->cf_first);
+  dfree(op->cf_ctr);
   for (auto& pr : op->prof_pending) {
     (void)hipEventDestroy(pr.a);
     (void)hipEventDestroy(pr.b);
@@ -1739,6 +1836,44 @@ int fw_set_async_input(fw_op* op, int enable) {
 
 void* fw_input_stream(fw_op* op) { return op ? (void*)input_stream_of(op) : nullptr; }
 
+namespace {
+// processWatermark of a ContinuousEventTimeTrigger handle: count -> (refuse | grow the row buffer) -> fire.  A window
+// fires once per timer <= min(wm, cleanup), so the rows of one advance are not bounded by the table: the counting pass
+// sums them first (it writes nothing), the host refuses the watermark when one window would fire more than 2^20
+// times -- the state is untouched, a smaller advance then works -- and makes room for the rest; only then the writing
+// pass runs.  The push before it is settled first (a suspended push has not finished updating the state).
+int cont_advance_watermark(fw_op* op, int64_t wm, int64_t* n_pending) {
+  int rc;
+  if ((rc = settle_quiet(op)) || (rc = maybe_restart_rows(op))) return rc;
+  if (wm > op->wm) {  // (a watermark that does not advance runs no timer)
+    HIP_OR_RETURN(op, hipMemsetAsync(op->cf_ctr, 0, 2 * sizeof(unsigned long long), op->stream));
+    fwdev::launch_cont_count(op->dc, wm, op->tb, op->cf_ctr, op->stream);
+    HIP_OR_RETURN(op, hipGetLastError());
+    unsigned long long ctr[2] = {0, 0};
+    HIP_OR_RETURN(op, hipMemcpyAsync(ctr, op->cf_ctr, sizeof ctr, hipMemcpyDeviceToHost, op->stream));
+    HIP_OR_RETURN(op, hipStreamSynchronize(op->stream));
+    if (ctr[1] > FW_CF_MAX_FIRINGS)
+      return set_err(op, FW_ERR_UNSUPPORTED,
+                     "watermark advance crosses more than 2^20 trigger intervals of a window (%llu firings of one "
+                     "window): advance in smaller steps", ctr[1]);
+    const int64_t rows = (int64_t)op->h_status->out_rows;
+    if (ctr[0] > (1ull << 40)) return set_err(op, FW_ERR_CAPACITY, "watermark advance would fire %llu rows", ctr[0]);
+    // (+ the table's slots: the room the ordered path of the next push counts on, set_slow_limit)
+    if ((rc = ensure_out_capacity(op, rows + (int64_t)ctr[0] + op->table_slots, rows))) return rc;
+    // (also with no row to fire: regions with a due cleanup timer are rewritten without the cleaned-up windows)
+    timed(op, K_FIRE, [&] { fwdev::launch_cont_fire(op->dc, wm, op->tb, op->out, op->d_status, op->stream); });
+    HIP_OR_RETURN(op, hipGetLastError());
+    op->wm = wm;  // HeapInternalTimerService.advanceWatermark: currentWatermark = time
+  }
+  op->fire_unsettled = true;
+  if ((rc = snapshot(op))) return rc;
+  if (!n_pending) return FW_OK;
+  if ((rc = settle(op))) return rc;
+  *n_pending = (int64_t)op->h_status->out_rows - op->out_base;
+  return FW_OK;
+}
+}  // namespace
+
 int fw_advance_watermark(fw_op* op, int64_t wm, int64_t* n_pending) {
   if (!op) return FW_ERR_ARG;
   HIP_OR_RETURN(op, hipSetDevice(op->device));
@@ -1750,6 +1885,7 @@ int fw_advance_watermark(fw_op* op, int64_t wm, int64_t* n_pending) {
     *n_pending = (int64_t)op->h_status->out_rows - op->out_base;
     return FW_OK;
   }
+  if (cont_iv(op->dc)) return cont_advance_watermark(op, wm, n_pending);
   // settled: the host knows the row count; unsettled: the ordered path left cap - table slots free
   // and an earlier watermark of the sequence found the buffer with that room as well
   if (!op->unsynced) {
@@ -1884,7 +2020,10 @@ int fw_get_stats(fw_op* op, fw_stats* o) {
   int rc = settle(op);
   if (rc) return rc;
   HIP_OR_RETURN(op, hipMemsetAsync(op->d_stats3, 0, 4 * sizeof(unsigned long long), op->stream));
-  fwdev::launch_table_stats(op->dc, op->tb, op->d_stats3, op->stream);
+  if (cont_iv(op->dc))
+    fwdev::launch_cont_stats(op->dc, op->tb, op->d_stats3, op->stream);
+  else
+    fwdev::launch_table_stats(op->dc, op->tb, op->d_stats3, op->stream);
   unsigned long long h3[4];
   HIP_OR_RETURN(op, hipMemcpyAsync(h3, op->d_stats3, sizeof h3, hipMemcpyDeviceToHost, op->stream));
   if ((rc = sync_status(op))) return rc;
@@ -1938,6 +2077,7 @@ static int fw_combine_extract_device_any(fw_op* op, int32_t world, fw_partials* 
 int fw_combine_extract_device(fw_op* op, int32_t world, fw_partials* out, int64_t cap, int64_t* counts,
                               int64_t* n) {
   if (!op || !n || world < 1 || (world > 1 && !counts)) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
+  if (cont_iv(op->dc)) return combine_refuses_continuous(op);
   if (!combine_eligible(op->cfg))
     return set_err(op, FW_ERR_UNSUPPORTED,
                    "combining needs tumbling windows or sliding windows kept as panes, the count/sum/min/max aggregate, no "
@@ -1990,6 +2130,7 @@ static int fw_combine_extract_device_any(fw_op* op, int32_t world, fw_partials* 
 
 int fw_push_partials_device(fw_op* op, const fw_partials* in, int64_t n) {
   if (!op || !in || n < 0) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
+  if (cont_iv(op->dc)) return combine_refuses_continuous(op);
   if (!combine_eligible(op->cfg))
     return set_err(op, FW_ERR_UNSUPPORTED,
                    "combining needs tumbling windows or sliding windows kept as panes, the count/sum/min/max aggregate, no "
@@ -2183,8 +2324,25 @@ int fw_snapshot_key_group(fw_op* op, int32_t kg, const fw_state_rows* dst, int64
   return fw_snapshot_key_group_blocks(op, kg, dst, nullptr, cap, n);
 }
 
+static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, uint8_t* blocks, int64_t* fire,
+                             int64_t cap, int64_t* n);
 int fw_snapshot_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* dst, uint8_t* blocks, int64_t cap,
                                  int64_t* n) {
+  if (op && cont_iv(op->dc))
+    return set_err(op, FW_ERR_UNSUPPORTED, "a ContinuousEventTimeTrigger handle's windows carry the trigger's fire time "
+                                           "and its timer: use fw_snapshot_key_group_fire");
+  return snapshot_rows_any(op, kg, dst, blocks, nullptr, cap, n);
+}
+int fw_snapshot_key_group_fire(fw_op* op, int32_t kg, const fw_state_rows* dst, int64_t* fire, int64_t cap, int64_t* n) {
+  if (op && !cont_iv(op->dc))
+    return set_err(op, FW_ERR_UNSUPPORTED, "fw_snapshot_key_group_fire needs a FW_TRIGGER_CONTINUOUS_EVENT_TIME handle "
+                                           "(others: fw_snapshot_key_group, fw_snapshot_key_group_blocks)");
+  if (op && dst && cap > 0 && !fire) return set_err(op, FW_ERR_ARG, "null fire_time column");
+  return snapshot_rows_any(op, kg, dst, nullptr, fire, cap, n);
+}
+// the rows of key group kg (fire != NULL: a ContinuousEventTimeTrigger handle's, with their fire times)
+static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, uint8_t* blocks, int64_t* fire,
+                             int64_t cap, int64_t* n) {
   if (op && op->cfg.assigner == FW_COUNT)
     return set_err(op, FW_ERR_UNSUPPORTED, "keyed-state snapshots of count windows are not offered");
   if (!op || !n) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
@@ -2204,18 +2362,25 @@ int fw_snapshot_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* dst
   for (int32_t v : live) bound += v;
   StateCols d{};
   uint8_t* acc = nullptr;
+  int64_t* dfire = nullptr;
+  const bool cont = cont_iv(c) != 0;
   auto release = [&]() {
     free_state_cols(d);
     dfree(d.blk);
     dfree(acc);
+    dfree(dfire);
   };
   if ((rc = alloc_state_cols(op, d, bound)) ||
+      (cont && dmalloc(&dfire, (size_t)std::max<int64_t>(bound, 1)) != hipSuccess && (rc = FW_ERR_HIP)) ||
       (bb && dmalloc(&d.blk, (size_t)std::max<int64_t>(bound, 1)) != hipSuccess && (rc = FW_ERR_HIP))) {
     release();
     return rc == FW_ERR_HIP ? set_err(op, rc, "snapshot: allocation failed") : rc;
   }
   HIP_OR_RETURN(op, hipMemsetAsync(op->d_stats3, 0, sizeof(unsigned long long), op->stream));
-  fwdev::launch_snapshot(c, op->tb, p0, np, d, op->d_stats3, op->stream);
+  if (cont)
+    fwdev::launch_cont_snapshot(c, op->tb, p0, np, d, dfire, op->d_stats3, op->stream);
+  else
+    fwdev::launch_snapshot(c, op->tb, p0, np, d, op->d_stats3, op->stream);
   unsigned long long got = 0;
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(&got, op->d_stats3, sizeof got, hipMemcpyDeviceToHost, op->stream);
@@ -2225,6 +2390,8 @@ int fw_snapshot_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* dst
     int64_t* ds[8] = {d.key, d.start, d.end, d.cnt, d.sum, d.mn, d.mx, d.timer};
     for (int i = 0; i < 8 && e == hipSuccess; i++)
       if (hs[i]) e = hipMemcpyAsync(hs[i], ds[i], got * sizeof(int64_t), hipMemcpyDeviceToHost, op->stream);
+    if (e == hipSuccess && cont && fire)
+      e = hipMemcpyAsync(fire, dfire, got * sizeof(int64_t), hipMemcpyDeviceToHost, op->stream);
     if (e == hipSuccess && bb) {  // the rows' accumulators in their snapshot form
       e = dmalloc(&acc, (size_t)(got * bb));
       if (e == hipSuccess) {
@@ -2303,7 +2470,24 @@ int fw_restore_key_group(fw_op* op, int32_t kg, const fw_state_rows* src, int64_
   return fw_restore_key_group_blocks(op, kg, src, nullptr, n);
 }
 
+static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, const uint8_t* blocks,
+                            const int64_t* fire, int64_t n);
 int fw_restore_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* src, const uint8_t* blocks, int64_t n) {
+  if (op && cont_iv(op->dc))
+    return set_err(op, FW_ERR_UNSUPPORTED, "a ContinuousEventTimeTrigger handle's windows carry the trigger's fire time "
+                                           "and its timer: use fw_restore_key_group_fire");
+  return restore_rows_any(op, kg, src, blocks, nullptr, n);
+}
+int fw_restore_key_group_fire(fw_op* op, int32_t kg, const fw_state_rows* src, const int64_t* fire, int64_t n) {
+  if (op && !cont_iv(op->dc))
+    return set_err(op, FW_ERR_UNSUPPORTED, "fw_restore_key_group_fire needs a FW_TRIGGER_CONTINUOUS_EVENT_TIME handle "
+                                           "(others: fw_restore_key_group, fw_restore_key_group_blocks)");
+  if (op && n > 0 && !fire) return set_err(op, FW_ERR_ARG, "null fire_time column");
+  return restore_rows_any(op, kg, src, nullptr, fire, n);
+}
+// (fire != NULL: a ContinuousEventTimeTrigger handle's rows, with their fire times)
+static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, const uint8_t* blocks,
+                            const int64_t* fire, int64_t n) {
   if (op && op->cfg.assigner == FW_COUNT)
     return set_err(op, FW_ERR_UNSUPPORTED, "keyed-state snapshots of count windows are not offered");
   if (!op || (n > 0 && !src) || n < 0) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
@@ -2316,6 +2500,24 @@ int fw_restore_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* src,
   const int64_t* hs[8] = {src->key, src->start, src->end, src->count, src->sum, src->min, src->max, src->timer};
   for (const int64_t* h : hs)
     if (!h) return set_err(op, FW_ERR_ARG, "null state column");
+  const bool cont = cont_iv(op->dc) != 0;
+  if (cont) {  // the rows as fw_snapshot_key_group_fire writes them, checked before anything changes
+    const int64_t iv = cont_iv(op->dc);
+    for (int64_t i = 0; i < n; i++) {
+      if (src->timer[i] & ~(int64_t)3)
+        return set_err(op, FW_ERR_ARG, "restore: row %lld: the timer column holds bit 0 (maxTimestamp's timer) and bit 1 "
+                                       "(the timer at the fire time)", (long long)i);
+      if (src->count[i] < 0 || src->end[i] != (int64_t)((uint64_t)src->start[i] + (uint64_t)op->dc.size))
+        return set_err(op, FW_ERR_ARG, "restore: row %lld is not a window of this operator's size", (long long)i);
+      const int64_t d = (int64_t)((uint64_t)fire[i] - (uint64_t)src->start[i]), span = op->dc.size + op->dc.lateness + 2 * iv;
+      if (fire[i] != INT64_MIN && (d > span || d < -span))
+        return set_err(op, FW_ERR_ARG, "restore: row %lld: fire time %lld is not one this trigger reaches in window "
+                                       "[%lld, %lld)", (long long)i, (long long)fire[i], (long long)src->start[i],
+                       (long long)src->end[i]);
+      if (fire[i] == INT64_MIN && (src->timer[i] & 2))
+        return set_err(op, FW_ERR_ARG, "restore: row %lld registers a timer at a null fire time", (long long)i);
+    }
+  }
   // first-element reduces: records pushed after the restore are numbered after every restored first
   // element, so the earlier element keeps winning in the caller's numbering
   // (minBy / maxBy: `max` is the selected element's ordinal, likewise)
@@ -2345,8 +2547,10 @@ int fw_restore_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* src,
   StateCols d{};
   int32_t* demand = nullptr;
   uint8_t* acc = nullptr;
+  int64_t* dfire = nullptr;
   auto fail = [&](int code) {
     free_state_cols(d);
+    dfree(dfire);
     dfree(demand);
     dfree(acc);
     dfree(d.blk);
@@ -2358,6 +2562,9 @@ int fw_restore_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* src,
   for (int i = 0; i < 8; i++)
     if (hipMemcpyAsync(ds[i], hs[i], n * sizeof(int64_t), hipMemcpyHostToDevice, op->stream) != hipSuccess)
       return fail(set_err(op, FW_ERR_HIP, "restore: copy failed"));
+  if (cont && (dmalloc(&dfire, (size_t)n) != hipSuccess ||
+               hipMemcpyAsync(dfire, fire, n * sizeof(int64_t), hipMemcpyHostToDevice, op->stream) != hipSuccess))
+    return fail(set_err(op, FW_ERR_HIP, "restore: copy failed"));
   // the rows' demand per partition: grow the table first if a region would pass its load limit
   const int32_t P = op->dc.P;
   if (dmalloc(&demand, (size_t)P) != hipSuccess || hipMemsetAsync(demand, 0, P * sizeof(int32_t), op->stream) != hipSuccess)
@@ -2411,7 +2618,10 @@ int fw_restore_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* src,
         hipMemcpyAsync(d_round, round_of.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, op->stream) != hipSuccess)
       return fail(set_err(op, FW_ERR_HIP, "restore: allocation failed"));
   }
-  fwdev::launch_restore(op->dc, kg, d, n, nullptr, op->tb, op->d_status, d_round, rounds, op->stream);
+  if (cont)
+    fwdev::launch_cont_restore(op->dc, kg, d, dfire, n, op->tb, op->d_status, d_round, rounds, op->stream);
+  else
+    fwdev::launch_restore(op->dc, kg, d, n, nullptr, op->tb, op->d_status, d_round, rounds, op->stream);
   const bool launched = hipGetLastError() == hipSuccess;
   rc = sync_status(op);
   dfree(d_round);
@@ -2875,6 +3085,7 @@ int fw_keyby_combine_push_device(fw_comm* c, fw_op* comb, fw_op* op, const int64
     if (op->cfg.key_group_start != (r * M + W - 1) / W || op->cfg.key_group_end != ((r + 1) * M - 1) / W)
       return set_err(op, FW_ERR_ARG, "the operator's KeyGroupRange is not subtask %d of %d's", r, W);
   }
+  if (cont_iv(op->dc) || cont_iv(comb->dc)) return combine_refuses_continuous(op);
   if (combine_config_tag(comb->cfg) != combine_config_tag(op->cfg))
     return set_err(op, FW_ERR_ARG,
                    "the combiner is configured differently (assigner, size, offset, value type, key kind, max "

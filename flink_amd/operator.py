@@ -17,12 +17,16 @@ import numpy as np
 
 from . import _native as N
 from .keygroups import KeyGroupRange
-from .windowing import CountSumMinMax, EventTimeTrigger, Trigger, WindowAssigner
+from .windowing import ContinuousEventTimeTrigger, CountSumMinMax, EventTimeTrigger, Trigger, WindowAssigner
 
 ROW_FIELDS = ("key", "start", "end", "count", "sum", "min", "max")
 ROW_DTYPE = np.dtype([(f, "<i8") for f in ROW_FIELDS] + [("epoch", "<i8")])
 STATE_FIELDS = ("key", "start", "end", "count", "sum", "min", "max", "timer")
 STATE_DTYPE = np.dtype([(f, "<i8") for f in STATE_FIELDS])
+# ContinuousEventTimeTrigger handles: the trigger's fire time per window (FIRE_NULL = null), and in `timer` bit 0 =
+# maxTimestamp's timer, bit 1 = the timer at the fire time (fw_snapshot_key_group_fire)
+FIRE_STATE_DTYPE = np.dtype(STATE_DTYPE.descr + [("fire_time", "<i8")])
+FIRE_NULL = -(1 << 63)
 SIDE_DTYPE = np.dtype([("key", "<i8"), ("ts", "<i8"), ("val", "<i8"), ("epoch", "<i8")])
 # list state per key group (fw_list_state): the lists and their elements concatenated in list order.  Snapshots of
 # GpuListWindowOperator (listwindow.py takes the two from here) and of a count-window GpuWindowOperator
@@ -48,9 +52,10 @@ class GpuWindowOperator:
                  key_group_range: KeyGroupRange = None, device=0, expected_entries=0, max_batch=0,
                  sub_partitions=0, async_input=True, no_panes=False):
         trigger = trigger or EventTimeTrigger.create()
-        if not isinstance(getattr(trigger, "nested", trigger), EventTimeTrigger):
-            raise ValueError("GpuWindowOperator takes EventTimeTrigger or PurgingTrigger.of(EventTimeTrigger); "
-                             "count triggers run on GpuListWindowOperator")
+        inner = getattr(trigger, "nested", trigger)
+        if not isinstance(inner, (EventTimeTrigger, ContinuousEventTimeTrigger)):
+            raise ValueError("GpuWindowOperator takes EventTimeTrigger, ContinuousEventTimeTrigger.of(interval) or "
+                             "PurgingTrigger.of(either); count triggers run on GpuListWindowOperator")
         if allowed_lateness < 0:
             raise ValueError("The allowed lateness cannot be negative.")
         kgr = key_group_range or KeyGroupRange(0, max_parallelism - 1)
@@ -74,6 +79,12 @@ class GpuWindowOperator:
                 c.row_aggregate[q] = w
         c.key_kind = _KEY_KINDS[key_type]
         c.purging = int(trigger.purging)
+        # early firings: fw_create refuses what this trigger is not offered for (sessions, count windows, every
+        # aggregate but count/sum/min/max) and names GpuListWindowOperator, which takes those
+        self._continuous = isinstance(inner, ContinuousEventTimeTrigger)
+        if self._continuous:
+            c.trigger = N.FW_TRIGGER_CONTINUOUS_EVENT_TIME
+            c.trigger_interval = inner.interval
         c.side_output = int(side_output)
         c.max_parallelism = max_parallelism
         c.key_group_start = kgr.start_key_group
@@ -502,6 +513,8 @@ class GpuWindowOperator:
     def state_dtype(self):
         """Row type of this operator's snapshots: STATE_DTYPE, plus `acc` (the accumulator block, fw_state_block_bytes
         bytes: HyperLogLog registers / the t-digest's centroids) for the HyperLogLog and t-digest aggregates."""
+        if self._continuous:  # the trigger's fire time rides with the window (fw_snapshot_key_group_fire)
+            return FIRE_STATE_DTYPE
         bb = N.lib().fw_state_block_bytes(self._h)
         return STATE_DTYPE if bb == 0 else np.dtype(STATE_DTYPE.descr + [("acc", "u1", (bb,))])
 
@@ -527,6 +540,18 @@ class GpuWindowOperator:
             for f in ec:
                 el[f] = ec[f]
             return lists, el
+        if self._continuous:
+            n = ctypes.c_int64()
+            N.check(L.fw_snapshot_key_group_fire(self._h, int(kg), None, None, 0, ctypes.byref(n)), self._h)
+            cols = {f: np.zeros(n.value, dtype=np.int64) for f in STATE_FIELDS + ("fire_time",)}
+            dst = N.FwStateRows(**{f: cols[f].ctypes.data for f in STATE_FIELDS})
+            got = ctypes.c_int64()
+            N.check(L.fw_snapshot_key_group_fire(self._h, int(kg), ctypes.byref(dst), cols["fire_time"].ctypes.data,
+                                                 n.value, ctypes.byref(got)), self._h)
+            out = np.zeros(got.value, dtype=FIRE_STATE_DTYPE)
+            for f in cols:
+                out[f] = cols[f][:got.value]
+            return out
         bb = L.fw_state_block_bytes(self._h)
         n = ctypes.c_int64()
         N.check(L.fw_snapshot_key_group_blocks(self._h, int(kg), None, None, 0, ctypes.byref(n)), self._h)
@@ -563,6 +588,15 @@ class GpuWindowOperator:
             return
         if elems is not None:
             raise ValueError("only count windows restore (lists, elems); this operator restores state_dtype() rows")
+        if self._continuous:
+            rows = np.ascontiguousarray(rows)
+            if rows.dtype.names is None or "fire_time" not in rows.dtype.names:
+                raise ValueError("rows of a ContinuousEventTimeTrigger operator carry `fire_time` (state_dtype())")
+            cols = {f: np.ascontiguousarray(rows[f], dtype=np.int64) for f in STATE_FIELDS + ("fire_time",)}
+            src = N.FwStateRows(**{f: cols[f].ctypes.data for f in STATE_FIELDS})
+            N.check(L.fw_restore_key_group_fire(self._h, int(kg), ctypes.byref(src), cols["fire_time"].ctypes.data,
+                                                len(rows)), self._h)
+            return
         bb = L.fw_state_block_bytes(self._h)
         rows = np.ascontiguousarray(rows)
         if bb and (rows.dtype.names is None or "acc" not in rows.dtype.names or rows.dtype["acc"].shape != (bb,)):

@@ -157,8 +157,9 @@ class EventTimeTrigger(Trigger):
 
 
 class PurgingTrigger(Trigger):
-    """PurgingTrigger.of(EventTimeTrigger.create()) (PurgingTrigger.java:45-59); around CountTrigger.of(n) or
-    ContinuousEventTimeTrigger.of(interval) for the window-contents operator only."""
+    """PurgingTrigger.of(EventTimeTrigger.create()) (PurgingTrigger.java:45-59); around
+    ContinuousEventTimeTrigger.of(interval) for both operators, around CountTrigger.of(n) for the window-contents
+    operator only."""
     purging = True
 
     def __init__(self, nested):
@@ -204,7 +205,8 @@ class CountTrigger(Trigger):
 class ContinuousEventTimeTrigger(Trigger):
     """ContinuousEventTimeTrigger.of(Time.milliseconds(interval)) (ContinuousEventTimeTrigger.java:39-151): early
     firings every `interval` ms of event time from the first element's interval on, and at the window's maxTimestamp;
-    for the window-contents operator (GpuListWindowOperator) over time, global and session windows."""
+    for the window-contents operator (GpuListWindowOperator) over time, global and session windows, and for the
+    aggregating operator (GpuWindowOperator) with the count/sum/min/max aggregate over tumbling and sliding windows."""
 
     def __init__(self, interval):
         interval = getattr(interval, "ms", interval)

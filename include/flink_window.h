@@ -198,8 +198,35 @@ typedef struct fw_config {
                                   ts - offset + slide < 0 off the slide grid, which the reference assigns
                                   size / slide + 1 windows; FW_ERR_DISPLACED); windows take it exactly.  Appended:
                                   no earlier offset moved */
-  int32_t pad1;
+  int32_t trigger;             /* FW_TRIGGER_EVENT_TIME (0, a zeroed field: EventTimeTrigger.java:37-73, the window's
+                                  default trigger) or FW_TRIGGER_CONTINUOUS_EVENT_TIME: the trigger argument of the
+                                  WindowOperator constructor (WindowOperator.java:179-212) set by
+                                  WindowedStream.trigger(ContinuousEventTimeTrigger.of(interval)); `purging` wraps
+                                  either in PurgingTrigger.  The constants are the list operator's, below.  (In the
+                                  former pad1 slot: no offset moved.) */
+  int64_t trigger_interval;    /* FW_TRIGGER_CONTINUOUS_EVENT_TIME: ContinuousEventTimeTrigger's interval in ms
+                                  (ContinuousEventTimeTrigger.java:42-50), > 0 (FW_ERR_ARG).  Appended. */
 } fw_config;
+
+/* ContinuousEventTimeTrigger on the aggregating operator (early firings: a window emits its running aggregate every
+ * `interval` of event time, ContinuousEventTimeTrigger.java:39-151).  Offered for FW_AGG_COUNT_SUM_MIN_MAX over every
+ * value type and key kind, FW_TUMBLING and FW_SLIDING, with allowed lateness, purging and side output, host and
+ * device pushes.  Such a handle keeps windows: no panes, dense regions, compact records or single pass.
+ *   Refused by fw_create (FW_ERR_UNSUPPORTED, before the GPU is touched): FW_SESSION (a merged session's fire time is
+ *   the minimum over its founders in arrival order: fw_list_create takes sessions under this trigger), FW_COUNT,
+ *   every other aggregate (the window-contents operator, fw_list_create, runs any function under this trigger), and
+ *   size + allowed_lateness + 2 * trigger_interval > 2^60 (the fire time rides in the entry as an offset from the
+ *   window's start).
+ *   fw_advance_watermark refuses an advance over which one window would fire more than 2^20 times
+ *   (FW_ERR_UNSUPPORTED, "2^20 trigger intervals"; nothing changed: advance in smaller steps).
+ *   A record with ts > Long.MAX_VALUE - interval (its first fire time ts - ts % interval + interval, or the timer
+ *   after it, wraps past Long.MAX_VALUE) is refused with FW_ERR_TIME_RANGE as the other timestamps at the ends of the long range are (host columns: the whole push, state
+ *   untouched; device columns: the record is left out and the settling call reports it).
+ *   The pre-shuffle combiner entry points refuse the handle (a combiner's partials carry no arrival order), and
+ *   fw_snapshot_key_group / fw_restore_key_group point to fw_snapshot_key_group_fire / fw_restore_key_group_fire.
+ *   fw_stats: keyed_state_entries counts the windows with contents (a purged window keeps its trigger state until its
+ *   cleanup time), event_time_timers the timers at maxTimestamp, at the fire time and at the cleanup time, coinciding
+ *   times once (HeapInternalTimerService keeps a set). */
 
 typedef struct fw_op fw_op;
 
@@ -406,6 +433,21 @@ int fw_snapshot_key_group_blocks(fw_op* op, int32_t key_group, const fw_state_ro
                                  int64_t cap, int64_t* n);
 int fw_restore_key_group_blocks(fw_op* op, int32_t key_group, const fw_state_rows* host_src,
                                 const uint8_t* host_blocks, int64_t n);
+
+/* The same for a FW_TRIGGER_CONTINUOUS_EVENT_TIME handle, whose windows carry the trigger's partitioned state: the
+ * "fire-time" ReducingState (ContinuousEventTimeTrigger.java:44-46, Min) and its timer (the heap backend snapshots both
+ * per key group, HeapKeyedStateBackend.java:370-381, InternalTimeServiceManager.java:114).  fire_time[i] is row i's
+ * fire time, Long.MIN_VALUE = null (as in the list operator's snapshots); in the `timer` column bit 0 is
+ * maxTimestamp's timer and bit 1 "the timer at the fire time is registered".  A window purged by PurgingTrigger is a
+ * row too (count 0) until its cleanup time: its fire time and timers are state.  Restore into any KeyGroupRange
+ * (rescaling) works as for the plain rows; a row whose (key, window) is present merges, the fire times by Min.
+ * fw_snapshot_key_group / fw_restore_key_group (and the _blocks forms) refuse such a handle with
+ * FW_ERR_UNSUPPORTED, and these two refuse every other handle.  (The heap-format bridge does not carry the
+ * trigger's state: DESIGN.md §7.) */
+int fw_snapshot_key_group_fire(fw_op* op, int32_t key_group, const fw_state_rows* host_dst, int64_t* host_fire_time,
+                               int64_t cap, int64_t* n);
+int fw_restore_key_group_fire(fw_op* op, int32_t key_group, const fw_state_rows* host_src,
+                              const int64_t* host_fire_time, int64_t n);
 
 /* Key routing (both sides of keyBy).
  *   fw_key_groups_device: kg[i] = KeyGroupRangeAssignment.assignToKeyGroup(key_i, maxParallelism)
