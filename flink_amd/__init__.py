@@ -26,4 +26,7 @@ def __getattr__(name):
     if name in ("GpuListWindowOperator", "SESSION_STATE_DTYPE"):
         from . import listwindow
         return getattr(listwindow, name)
+    if name in ("GpuWindowJoin", "PAIR_DTYPE"):
+        from . import join
+        return getattr(join, name)
     raise AttributeError(name)

@@ -112,6 +112,18 @@ class FwListConfig(ctypes.Structure):
          ("trigger_interval", ctypes.c_int64)]
 
 
+FW_JOIN_NONE, FW_JOIN_COGROUP, FW_JOIN_INNER = 0, 1, 2
+FW_ORD_SIDE = 1 << 62  # an element's input on a join handle: bit 62 of its arrival ordinal (set = input 2)
+
+
+class FwJoinConfig(ctypes.Structure):
+    _fields_ = [("join", ctypes.c_int32), ("pad", ctypes.c_int32), ("max_join_pairs", ctypes.c_int64)]
+
+
+class FwJoinPairs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("row", "idx1", "idx2", "val1", "val2")]
+
+
 class FwListRows(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("key", "start", "end", "count", "sum", "min", "max", "first",
                                                "elem_off")]
@@ -197,10 +209,20 @@ SIGNATURES = {
     "fw_wire_encode_device": (ctypes.c_int, [VP, ctypes.POINTER(FwRows), ctypes.c_int64, ctypes.c_int32, VP,
                                              ctypes.c_int64, I64P]),
     "fw_list_create": (ctypes.c_int, [ctypes.POINTER(FwListConfig), ctypes.POINTER(VP)]),
+    "fw_list_create_join": (ctypes.c_int, [ctypes.POINTER(FwListConfig), ctypes.POINTER(FwJoinConfig),
+                                           ctypes.POINTER(VP)]),
     "fw_list_destroy": (None, [VP]),
     "fw_list_last_error": (ctypes.c_char_p, [VP]),
     "fw_list_push_batch": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_int64]),
     "fw_list_push_batch_device": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_int64]),
+    "fw_list_push_batch_side": (ctypes.c_int, [VP, ctypes.c_int32, VP, VP, VP, VP, ctypes.c_int64]),
+    "fw_list_push_batch_side_device": (ctypes.c_int, [VP, ctypes.c_int32, VP, VP, VP, VP, ctypes.c_int64]),
+    "fw_list_join_pending": (ctypes.c_int, [VP, I64P, I64P, I64P]),
+    "fw_list_drain_join": (ctypes.c_int, [VP, ctypes.POINTER(FwListRows), VP, ctypes.c_int64,
+                                          ctypes.POINTER(FwListElems), ctypes.c_int64, ctypes.POINTER(FwJoinPairs),
+                                          ctypes.c_int64, I64P, I64P, I64P]),
+    "fw_list_join_device": (ctypes.c_int, [VP, ctypes.POINTER(FwListRows), ctypes.POINTER(VP),
+                                           ctypes.POINTER(FwListElems), ctypes.POINTER(FwJoinPairs), I64P, I64P, I64P]),
     "fw_list_advance_watermark": (ctypes.c_int, [VP, ctypes.c_int64, I64P]),
     "fw_list_pending": (ctypes.c_int, [VP, I64P, I64P, I64P]),
     "fw_list_drain": (ctypes.c_int, [VP, ctypes.POINTER(FwListRows), ctypes.c_int64, ctypes.POINTER(FwListElems),

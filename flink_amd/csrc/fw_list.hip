@@ -23,6 +23,9 @@
 // same way, and drops the cleaned-up ones.
 // ContinuousEventTimeTrigger (triggers/ContinuousEventTimeTrigger.java:39-151) adds a fire time per group (gfire) and
 // a second timer: a watermark then fires a list once per due timer ("ContinuousEventTimeTrigger" below).
+// Window joins (fw_list_create_join; "window joins" below): the same operator over the tagged union of two inputs, an
+// element's input in bit 62 of its ordinal, and a stage over the pending output that splits every firing by input and
+// forms the pairs (CoGroupedStreams.java:273-304, :657-685; JoinedStreams.java:387-404).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1797,6 +1800,163 @@ __global__ __launch_bounds__(256) void k_sr_apply(LCfg c, LState S, int32_t kg, 
   block_add(&S.ctr->live_groups, ins);
 }
 
+// ---------------------------------------------------------------- window joins (include/flink_window.h "window joins")
+// CoGroupWindowFunction.apply (api/datastream/CoGroupedStreams.java:657-685) and JoinCoGroupFunction.coGroup
+// (JoinedStreams.java:387-404) over the pending output: the fired rows S.r* and their elements S.e*, whose ordinals
+// carry the input in FW_ORD_SIDE.  Nothing here reads or writes operator state.
+//   split   element-parallel.  Every element learns its row (the rows' elements tile the pending elements, but not in
+//           row order: the row index is scattered to each row's first element and carried forward by a scan) and its
+//           rank among the row's elements of its input (a prefix sum of "is input 1" over all pending elements, minus
+//           its value at the row's start); the element goes to off + rank (input 1) or off + n_first + rank (input 2).
+//   count   per row n_first and the 64-bit pair count, then an exclusive scan over the rows.
+//   emit    a workgroup takes JCHUNK consecutive pairs of the global pair index space, finds the row of its first pair
+//           by one binary search in the scanned offsets (upper bound - 1: it lands behind runs of rows without pairs)
+//           and its lanes walk on from there.  A lane writes two consecutive pairs per step, so each of the five
+//           columns is stored as one contiguous run of 16-byte stores per wave (8-byte stores run at 0.54-0.70x the
+//           16-byte rate on this part); val1 / val2 come from the lines its neighbours read.  (i, j) are divided out
+//           once when a lane enters a row and stepped afterwards.
+struct JState {
+  int32_t *erow_in, *erow;  // per element: its row at the row's first element / at every element
+  int64_t* c0;              // ne + 1: elements of input 1 before each element
+  int64_t *pts, *pval, *pord;  // the partitioned elements
+  int64_t *nfirst, *npair, *poff;  // per row; poff: nr + 1 scanned pair offsets
+  int64_t *prow, *pi1, *pi2, *pv1, *pv2;
+};
+struct JLast {  // the last row index seen so far (-1: none)
+  __host__ __device__ int32_t operator()(int32_t a, int32_t b) const { return b >= 0 ? b : a; }
+};
+__global__ __launch_bounds__(256) void k_join_heads(LState S, JState J, int64_t nr, int64_t ne) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nr; r += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t f = S.rfirst[r];
+    if (f >= 0) S.rfirst[r] = f & ~FW_ORD_SIDE;  // the rows' first column is the plain ordinal
+    const int64_t off = S.roff[r], cnt = S.rcnt[r];
+    if (cnt > 0 && off >= 0 && off + cnt <= ne) J.erow_in[off] = (int32_t)r;
+  }
+}
+__global__ __launch_bounds__(256) void k_join_flags(LState S, int64_t ne, int64_t* __restrict__ f) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < ne; e += (int64_t)gridDim.x * blockDim.x)
+    f[e] = S.eord[e] & FW_ORD_SIDE ? 0 : 1;
+}
+__global__ __launch_bounds__(256) void k_join_count(LState S, JState J, int64_t nr, int64_t ne, bool inner) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nr; r += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t off = S.roff[r], cnt = S.rcnt[r];
+    const int64_t n1 = cnt > 0 && off >= 0 && off + cnt <= ne ? J.c0[off + cnt] - J.c0[off] : 0;
+    J.nfirst[r] = n1;
+    J.npair[r] = inner ? n1 * (cnt - n1) : 0;
+  }
+}
+__global__ __launch_bounds__(256) void k_join_scatter(LState S, JState J, int64_t ne) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < ne; e += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t r = J.erow[e];
+    if (r < 0) continue;
+    const int64_t off = S.roff[r];
+    if (e - off >= S.rcnt[r]) continue;  // (not an element of any pending row)
+    const int64_t rank0 = J.c0[e] - J.c0[off], o = S.eord[e];
+    const int64_t d = o & FW_ORD_SIDE ? off + J.nfirst[r] + (e - off - rank0) : off + rank0;
+    J.pts[d] = S.ets[e];
+    J.pval[d] = S.eval[e];
+    J.pord[d] = o;
+  }
+}
+__global__ __launch_bounds__(256) void k_join_first(LState S, int64_t nr) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nr; r += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t f = S.rfirst[r];
+    if (f >= 0) S.rfirst[r] = f & ~FW_ORD_SIDE;
+  }
+}
+
+constexpr int JSTEPS = 8;
+constexpr int64_t JCHUNK = 256 * 2 * JSTEPS;  // pairs per workgroup round
+// the first index in [lo, hi] whose offset is > q (poff[hi] > q)
+__device__ __forceinline__ int64_t j_upper(const int64_t* __restrict__ poff, int64_t lo, int64_t hi, int64_t q) {
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (poff[mid] > q) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+struct JCur {
+  int64_t r, q, hi, n2, i, j, off1, off2;
+};
+// the cursor at pair q of row r (poff[r] <= q < poff[r + 1]): one division
+__device__ __forceinline__ void j_enter(JCur& c, const LState& S, const JState& J, int64_t r, int64_t q) {
+  const int64_t lo = J.poff[r], n1 = J.nfirst[r];
+  c.r = r;
+  c.q = q;
+  c.hi = J.poff[r + 1];
+  c.n2 = S.rcnt[r] - n1;
+  const uint64_t d = (uint64_t)(q - lo), n2 = (uint64_t)c.n2;
+  if (((d | n2) >> 32) == 0) {
+    c.i = (int64_t)((uint32_t)d / (uint32_t)n2);
+    c.j = (int64_t)((uint32_t)d % (uint32_t)n2);
+  } else {
+    c.i = (int64_t)(d / n2);
+    c.j = (int64_t)(d - (uint64_t)c.i * n2);
+  }
+  c.off1 = S.roff[r];
+  c.off2 = c.off1 + n1;
+}
+// forward to pair q >= c.q, less than JCHUNK ahead
+__device__ __forceinline__ void j_seek(JCur& c, const LState& S, const JState& J, int64_t nr, int64_t q) {
+  if (q < c.hi) {
+    c.j += q - c.q;
+    c.q = q;
+    if (c.j >= c.n2) {
+      if (c.n2 >= JCHUNK) {  // at most one wrap
+        c.j -= c.n2;
+        c.i++;
+      } else {  // (j < 2 * JCHUNK: 32-bit)
+        const uint32_t w = (uint32_t)c.j / (uint32_t)c.n2;
+        c.i += w;
+        c.j -= (int64_t)w * c.n2;
+      }
+    }
+    return;
+  }
+  int64_t r = c.r + 1;  // a few rows on, else a search (it steps over runs of rows without pairs)
+  for (int s = 0; s < 4 && J.poff[r + 1] <= q; s++) r++;
+  if (J.poff[r + 1] <= q) r = j_upper(J.poff, r + 1, nr, q) - 1;
+  j_enter(c, S, J, r, q);
+}
+__global__ __launch_bounds__(256) void k_join_emit(LState S, JState J, int64_t nr, int64_t total) {
+  __shared__ int64_t r0s;
+  for (int64_t q0 = (int64_t)blockIdx.x * JCHUNK; q0 < total; q0 += (int64_t)gridDim.x * JCHUNK) {
+    __syncthreads();
+    if (threadIdx.x == 0) r0s = j_upper(J.poff, 0, nr, q0) - 1;
+    __syncthreads();
+    int64_t q = q0 + 2 * threadIdx.x;
+    if (q >= total) continue;
+    JCur c;
+    {
+      int64_t r = r0s;  // the workgroup's first row; this lane's first pair is at most 510 pairs on
+      for (int s = 0; s < 4 && J.poff[r + 1] <= q; s++) r++;
+      if (J.poff[r + 1] <= q) r = j_upper(J.poff, r + 1, nr, q) - 1;
+      j_enter(c, S, J, r, q);
+    }
+#pragma unroll 2
+    for (int s = 0; s < JSTEPS && q < total; s++, q += 512) {
+      if (s) j_seek(c, S, J, nr, q);
+      const int64_t ra = c.r, ia = c.off1 + c.i, ja = c.off2 + c.j;
+      const int64_t va = J.pval[ia], wa = J.pval[ja];
+      if (q + 1 < total) {
+        j_seek(c, S, J, nr, q + 1);
+        const int64_t ib = c.off1 + c.i, jb = c.off2 + c.j;
+        *reinterpret_cast<longlong2*>(J.prow + q) = make_longlong2(ra, c.r);
+        *reinterpret_cast<longlong2*>(J.pi1 + q) = make_longlong2(ia, ib);
+        *reinterpret_cast<longlong2*>(J.pi2 + q) = make_longlong2(ja, jb);
+        *reinterpret_cast<longlong2*>(J.pv1 + q) = make_longlong2(va, J.pval[ib]);
+        *reinterpret_cast<longlong2*>(J.pv2 + q) = make_longlong2(wa, J.pval[jb]);
+      } else {
+        J.prow[q] = ra;
+        J.pi1[q] = ia;
+        J.pi2[q] = ja;
+        J.pv1[q] = va;
+        J.pv2[q] = wa;
+      }
+    }
+  }
+}
+
 unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256)); }
 
 template <class T>
@@ -1842,6 +2002,14 @@ struct fw_list {
   unsigned long long* ss_scr = nullptr;  // fw_list_snapshot_sessions' per-slot scratch (4 x ss_cap)
   int64_t ss_cap = 0;
   bool poisoned = false;  // a session restore failed after it began to apply: pushes, watermarks and snapshots refuse
+  // window joins (join != 0; nothing of it is allocated otherwise, and all of it on the first join call)
+  int join = FW_JOIN_NONE;
+  int64_t push_tag = 0;  // FW_ORD_SIDE while a batch of input 2 is pushed: or-ed into the batch's ordinal base
+  JState J{};
+  int64_t jecap = 0, jrcap = 0, jpcap = 0, max_pairs = 0;
+  // what the split / the pairs in J cover (-1: nothing; pending output only grows between two drains)
+  int64_t j_rows = -1, j_elems = -1, j_total = 0;
+  bool j_emitted = false;
 };
 
 namespace {
@@ -2260,7 +2428,7 @@ int sl_push(fw_list* op, const int64_t* key, const int64_t* ts, const int64_t* v
   LHIP(op, rocprim::radix_sort_pairs(op->tmp, bytes, op->sk, op->sk2, op->si, op->si2, (size_t)n, 0, 64, op->stream));
   const int64_t base = op->n_log;
   hipLaunchKernelGGL(k_sl_place, dim3(grid_for(n)), dim3(256), 0, op->stream, op->S, ts, val, op->sk2, op->si2, n, base,
-                     op->ord_base, op->flags8);
+                     op->ord_base | op->push_tag, op->flags8);
   int64_t nruns = 0;
   LRET(select_positions(op, op->flags8, n, op->seg, &nruns));  // (reads the counters: flags are current)
   LRET(sl_check_flags(op));
@@ -2382,7 +2550,8 @@ int push_device(fw_list* op, const int64_t* key, const int64_t* ts, const int64_
   for (int round = 0;; round++) {
     LHIP(op, hipMemsetAsync(&op->S.ctr->flags, 0, 8, op->stream));  // flags, need_seq
     hipLaunchKernelGGL(k_lp_append, dim3(grid_for(n)), dim3(256), 0, op->stream, op->c, op->S, key, ts, val, kh, n,
-                       op->wm, op->wcnt, op->woff, base, op->ord_base, (unsigned long long)(op->gcap / 4 * 3));
+                       op->wm, op->wcnt, op->woff, base, op->ord_base | op->push_tag,
+                       (unsigned long long)(op->gcap / 4 * 3));
     LRET(read_ctr(op));
     if (!(op->h_ctr->flags & LF_MAP_FULL)) break;
     if (round > 40) return set_err(op, FW_ERR_CAPACITY, "list state map full");
@@ -2428,11 +2597,198 @@ int32_t host_key_group(const LCfg& cfg, int64_t k) {
   return r % cfg.max_par;
 }
 
+
+// ---------------------------------------------------------------- window joins: the stage over the pending output
+void join_free(fw_list* op) {
+  JState& J = op->J;
+  dfree(J.erow_in);
+  dfree(J.erow);
+  for (int64_t** p : {&J.c0, &J.pts, &J.pval, &J.pord, &J.nfirst, &J.npair, &J.poff, &J.prow, &J.pi1, &J.pi2, &J.pv1,
+                      &J.pv2})
+    dfree(*p);
+  op->jecap = op->jrcap = op->jpcap = 0;
+}
+// split and count over all pending rows and elements (the counters are read first); j_total = the pending pairs
+int join_split(fw_list* op) {
+  LRET(read_ctr(op));
+  const int64_t nr = (int64_t)op->h_ctr->rows, ne = (int64_t)op->h_ctr->elems;
+  if (nr == op->j_rows && ne == op->j_elems) return FW_OK;  // nothing fired since
+  JState& J = op->J;
+  if (ne > op->jecap) {
+    const int64_t cap = std::max<int64_t>({ne, op->jecap * 2, 1024});
+    dfree(J.erow_in);
+    dfree(J.erow);
+    for (int64_t** p : {&J.c0, &J.pts, &J.pval, &J.pord}) dfree(*p);
+    op->jecap = 0;
+    LHIP(op, dmalloc(&J.erow_in, (size_t)cap));
+    LHIP(op, dmalloc(&J.erow, (size_t)cap));
+    LHIP(op, dmalloc(&J.c0, (size_t)cap + 1));
+    for (int64_t** p : {&J.pts, &J.pval, &J.pord}) LHIP(op, dmalloc(p, (size_t)cap));
+    op->jecap = cap;
+  }
+  if (nr > op->jrcap) {
+    const int64_t cap = std::max<int64_t>({nr, op->jrcap * 2, 1024});
+    for (int64_t** p : {&J.nfirst, &J.npair, &J.poff}) dfree(*p);
+    op->jrcap = 0;
+    LHIP(op, dmalloc(&J.nfirst, (size_t)cap));
+    LHIP(op, dmalloc(&J.npair, (size_t)cap));
+    LHIP(op, dmalloc(&J.poff, (size_t)cap + 1));
+    op->jrcap = cap;
+  }
+  op->j_rows = op->j_elems = -1;
+  op->j_emitted = false;
+  op->j_total = 0;
+  if (nr) {
+    const bool inner = op->join == FW_JOIN_INNER;
+    size_t bytes = 0;
+    if (ne) {
+      LHIP(op, hipMemsetAsync(J.erow_in, 0xff, (size_t)ne * 4, op->stream));
+      hipLaunchKernelGGL(k_join_heads, dim3(grid_for(nr)), dim3(256), 0, op->stream, op->S, J, nr, ne);
+      LHIP(op, rocprim::inclusive_scan(nullptr, bytes, J.erow_in, J.erow, (size_t)ne, JLast(), op->stream));
+      LRET(ensure_tmp(op, bytes));
+      bytes = op->tmp_bytes;
+      LHIP(op, rocprim::inclusive_scan(op->tmp, bytes, J.erow_in, J.erow, (size_t)ne, JLast(), op->stream));
+      // "is input 1" per element (in pts, which the scatter fills afterwards), summed into c0[1 .. ne]
+      hipLaunchKernelGGL(k_join_flags, dim3(grid_for(ne)), dim3(256), 0, op->stream, op->S, ne, J.pts);
+      LHIP(op, hipMemsetAsync(J.c0, 0, 8, op->stream));
+      LHIP(op, rocprim::inclusive_scan(nullptr, bytes, J.pts, J.c0 + 1, (size_t)ne, rocprim::plus<int64_t>(),
+                                       op->stream));
+      LRET(ensure_tmp(op, bytes));
+      bytes = op->tmp_bytes;
+      LHIP(op, rocprim::inclusive_scan(op->tmp, bytes, J.pts, J.c0 + 1, (size_t)ne, rocprim::plus<int64_t>(),
+                                       op->stream));
+    } else {
+      hipLaunchKernelGGL(k_join_first, dim3(grid_for(nr)), dim3(256), 0, op->stream, op->S, nr);
+    }
+    hipLaunchKernelGGL(k_join_count, dim3(grid_for(nr)), dim3(256), 0, op->stream, op->S, J, nr, ne, inner);
+    LHIP(op, hipMemsetAsync(J.poff, 0, 8, op->stream));
+    LHIP(op, rocprim::inclusive_scan(nullptr, bytes, J.npair, J.poff + 1, (size_t)nr, rocprim::plus<int64_t>(),
+                                     op->stream));
+    LRET(ensure_tmp(op, bytes));
+    bytes = op->tmp_bytes;
+    LHIP(op, rocprim::inclusive_scan(op->tmp, bytes, J.npair, J.poff + 1, (size_t)nr, rocprim::plus<int64_t>(),
+                                     op->stream));
+    if (ne) hipLaunchKernelGGL(k_join_scatter, dim3(grid_for(ne)), dim3(256), 0, op->stream, op->S, J, ne);
+    LHIP(op, hipGetLastError());
+    LHIP(op, hipMemcpyAsync(&op->j_total, J.poff + nr, 8, hipMemcpyDeviceToHost, op->stream));
+    LHIP(op, hipStreamSynchronize(op->stream));
+  }
+  op->j_rows = nr;
+  op->j_elems = ne;
+  return FW_OK;
+}
+// the pairs of the split (FW_JOIN_INNER), unless they are there already
+int join_emit(fw_list* op) {
+  if (op->j_emitted || op->j_total == 0) return FW_OK;
+  if (op->j_total > op->max_pairs)
+    return set_err(op, FW_ERR_CAPACITY,
+                   "%lld pending pairs exceed max_join_pairs %lld: nothing was materialised or drained; drain the "
+                   "coGroup form with pairs == NULL, or drain more often",
+                   (long long)op->j_total, (long long)op->max_pairs);
+  JState& J = op->J;
+  if (op->j_total > op->jpcap) {
+    const int64_t cap = std::min<int64_t>(op->max_pairs, std::max<int64_t>({op->j_total, op->jpcap * 2, 4096}));
+    for (int64_t** p : {&J.prow, &J.pi1, &J.pi2, &J.pv1, &J.pv2}) dfree(*p);
+    op->jpcap = 0;
+    for (int64_t** p : {&J.prow, &J.pi1, &J.pi2, &J.pv1, &J.pv2})
+      if (dmalloc(p, (size_t)cap) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(op, FW_ERR_CAPACITY, "no memory for %lld pairs: drain the coGroup form with pairs == NULL",
+                       (long long)cap);
+      }
+    op->jpcap = cap;
+  }
+  const unsigned grid = (unsigned)std::min<int64_t>(16384, (op->j_total + JCHUNK - 1) / JCHUNK);
+  hipLaunchKernelGGL(k_join_emit, dim3(grid), dim3(256), 0, op->stream, op->S, J, op->j_rows, op->j_total);
+  LHIP(op, hipGetLastError());
+  op->j_emitted = true;
+  return FW_OK;
+}
+int join_handle(fw_list* op) {
+  if (!op) return FW_ERR_ARG;
+  if (!op->join) return set_err(op, FW_ERR_ARG, "the handle was created without a join");
+  (void)hipSetDevice(op->device);
+  if (op->poisoned) return set_err(op, FW_ERR_STATE, "the handle is unusable: a session restore failed half-way");
+  return FW_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
-int fw_list_create(const fw_list_config* cfg, fw_list** out) {
+int fw_list_join_pending(fw_list* op, int64_t* n_rows, int64_t* n_elems, int64_t* n_pairs) {
+  LRET(join_handle(op));
+  LRET(join_split(op));
+  if (n_rows) *n_rows = op->j_rows;
+  if (n_elems) *n_elems = op->j_elems;
+  if (n_pairs) *n_pairs = op->j_total;
+  return FW_OK;
+}
+
+int fw_list_drain_join(fw_list* op, const fw_list_rows* rows, int64_t* n_first, int64_t cap_rows,
+                       const fw_list_elems* elems, int64_t cap_elems, const fw_join_pairs* pairs, int64_t cap_pairs,
+                       int64_t* n_rows, int64_t* n_elems, int64_t* n_pairs) {
+  LRET(join_handle(op));
+  LRET(join_split(op));
+  const int64_t nr = op->j_rows, ne = op->j_elems, np = op->j_total;
+  if (n_rows) *n_rows = nr;
+  if (n_elems) *n_elems = ne;
+  if (n_pairs) *n_pairs = np;
+  if ((nr && !rows) || (ne && !elems)) return set_err(op, FW_ERR_ARG, "rows and elems are required");
+  if (nr > cap_rows || ne > cap_elems || (pairs && np > cap_pairs))
+    return set_err(op, FW_ERR_CAPACITY, "output too small");
+  if (pairs) LRET(join_emit(op));
+  const JState& J = op->J;
+  if (nr) {
+    const int64_t* src[] = {op->S.rkey, op->S.rstart, op->S.rend, op->S.rcnt, op->S.rsum, op->S.rmin, op->S.rmax,
+                            op->S.rfirst, op->S.roff, J.nfirst};
+    int64_t* dst[] = {rows->key, rows->start, rows->end, rows->count, rows->sum, rows->min, rows->max, rows->first,
+                      rows->elem_off, n_first};
+    for (int i = 0; i < 10; i++)
+      if (dst[i]) LHIP(op, hipMemcpyAsync(dst[i], src[i], (size_t)nr * 8, hipMemcpyDeviceToHost, op->stream));
+  }
+  if (ne) {
+    const int64_t* es[] = {J.pts, J.pval, J.pord};
+    int64_t* ed[] = {elems->ts, elems->val, elems->ordinal};
+    for (int i = 0; i < 3; i++)
+      if (ed[i]) LHIP(op, hipMemcpyAsync(ed[i], es[i], (size_t)ne * 8, hipMemcpyDeviceToHost, op->stream));
+  }
+  if (pairs && np) {
+    const int64_t* ps[] = {J.prow, J.pi1, J.pi2, J.pv1, J.pv2};
+    int64_t* pd[] = {pairs->row, pairs->idx1, pairs->idx2, pairs->val1, pairs->val2};
+    for (int i = 0; i < 5; i++)
+      if (pd[i]) LHIP(op, hipMemcpyAsync(pd[i], ps[i], (size_t)np * 8, hipMemcpyDeviceToHost, op->stream));
+  }
+  LHIP(op, hipMemsetAsync(&op->S.ctr->rows, 0, 16, op->stream));  // rows, elems
+  LHIP(op, hipStreamSynchronize(op->stream));
+  op->fired_total += nr;
+  op->h_ctr->rows = op->h_ctr->elems = 0;
+  op->j_rows = op->j_elems = -1;
+  return FW_OK;
+}
+
+int fw_list_join_device(fw_list* op, fw_list_rows* rows, int64_t** n_first, fw_list_elems* elems, fw_join_pairs* pairs,
+                        int64_t* n_rows, int64_t* n_elems, int64_t* n_pairs) {
+  LRET(join_handle(op));
+  LRET(join_split(op));
+  if (n_rows) *n_rows = op->j_rows;
+  if (n_elems) *n_elems = op->j_elems;
+  if (n_pairs) *n_pairs = op->j_total;
+  if (pairs) LRET(join_emit(op));
+  LHIP(op, hipStreamSynchronize(op->stream));
+  const JState& J = op->J;
+  if (rows)
+    *rows = fw_list_rows{op->S.rkey, op->S.rstart, op->S.rend, op->S.rcnt, op->S.rsum, op->S.rmin, op->S.rmax,
+                         op->S.rfirst, op->S.roff};
+  if (n_first) *n_first = J.nfirst;
+  if (elems) *elems = fw_list_elems{J.pts, J.pval, J.pord};
+  if (pairs) *pairs = fw_join_pairs{J.prow, J.pi1, J.pi2, J.pv1, J.pv2};
+  return FW_OK;
+}
+
+int fw_list_create(const fw_list_config* cfg, fw_list** out) { return fw_list_create_join(cfg, nullptr, out); }
+
+int fw_list_create_join(const fw_list_config* cfg, const fw_join_config* jcfg, fw_list** out) {
   if (!cfg || !out) return FW_ERR_ARG;
   *out = nullptr;
   fw_list* op = new fw_list();
@@ -2469,6 +2825,14 @@ int fw_list_create(const fw_list_config* cfg, fw_list** out) {
   if (c.evictor == FW_EVICT_COUNT && c.evict_count < 0) return fail(FW_ERR_ARG, "CountEvictor count must be >= 0");
   if (c.value_type < FW_VAL_I64 || c.value_type > FW_VAL_F32) return fail(FW_ERR_ARG, "unknown value type");
   if (c.key_kind < FW_KEY_LONG || c.key_kind > FW_KEY_HASHED) return fail(FW_ERR_ARG, "unknown key kind");
+  const fw_join_config jc = jcfg ? *jcfg : fw_join_config{FW_JOIN_NONE, 0, 0};
+  if (jc.join < FW_JOIN_NONE || jc.join > FW_JOIN_INNER)
+    return fail(FW_ERR_ARG, "join must be FW_JOIN_NONE, FW_JOIN_COGROUP or FW_JOIN_INNER");
+  if (jc.join != FW_JOIN_NONE && !c.emit_contents)
+    return fail(FW_ERR_ARG, "a window join reads the contents of every firing: emit_contents must be 1");
+  if (jc.max_join_pairs < 0) return fail(FW_ERR_ARG, "max_join_pairs must be >= 0");
+  op->join = jc.join;
+  op->max_pairs = jc.max_join_pairs > 0 ? jc.max_join_pairs : int64_t(1) << 30;
   const int32_t mp = c.max_parallelism ? c.max_parallelism : 128;
   const int32_t kg0 = c.key_group_start < 0 ? 0 : c.key_group_start;
   const int32_t kg1 = c.key_group_end < 0 ? mp - 1 : c.key_group_end;
@@ -2541,6 +2905,7 @@ void fw_list_destroy(fw_list* op) {
   dfree(op->sprog);
   dfree(op->pslot);
   dfree(op->ss_scr);
+  join_free(op);
   for (int64_t** p : {&op->S.rkey, &op->S.rstart, &op->S.rend, &op->S.rcnt, &op->S.rsum, &op->S.rmin, &op->S.rmax,
                       &op->S.rfirst, &op->S.roff, &op->S.ets, &op->S.eval, &op->S.eord, &op->S.skey, &op->S.sts,
                       &op->S.sval, &op->in_key, &op->in_ts, &op->in_val})
@@ -2567,6 +2932,28 @@ void fw_list_destroy(fw_list* op) {
 }
 
 const char* fw_list_last_error(const fw_list* op) { return op ? op->err.c_str() : "null handle"; }
+
+// a batch of one input of a join handle: its ordinals carry the input (FW_ORD_SIDE) from the ordinal base on
+int fw_list_push_batch_side_device(fw_list* op, int32_t side, const int64_t* key, const int64_t* ts, const void* val,
+                                   const int32_t* key_hash, int64_t n) {
+  if (!op) return FW_ERR_ARG;
+  if (side != 0 && side != 1) return set_err(op, FW_ERR_ARG, "side must be 0 (input 1) or 1 (input 2)");
+  if (!op->join) return set_err(op, FW_ERR_ARG, "a side push needs a handle created with a join");
+  op->push_tag = side ? FW_ORD_SIDE : 0;
+  const int rc = fw_list_push_batch_device(op, key, ts, val, key_hash, n);
+  op->push_tag = 0;
+  return rc;
+}
+int fw_list_push_batch_side(fw_list* op, int32_t side, const int64_t* key, const int64_t* ts, const void* val,
+                            const int32_t* key_hash, int64_t n) {
+  if (!op) return FW_ERR_ARG;
+  if (side != 0 && side != 1) return set_err(op, FW_ERR_ARG, "side must be 0 (input 1) or 1 (input 2)");
+  if (!op->join) return set_err(op, FW_ERR_ARG, "a side push needs a handle created with a join");
+  op->push_tag = side ? FW_ORD_SIDE : 0;
+  const int rc = fw_list_push_batch(op, key, ts, val, key_hash, n);
+  op->push_tag = 0;
+  return rc;
+}
 
 int fw_list_push_batch_device(fw_list* op, const int64_t* key, const int64_t* ts, const void* val,
                               const int32_t* key_hash, int64_t n) {
@@ -2654,6 +3041,8 @@ int fw_list_drain(fw_list* op, const fw_list_rows* rows, int64_t cap_rows, const
   if (n_rows) *n_rows = nr;
   if (n_elems) *n_elems = ne;
   if (nr > cap_rows || (ne && (!elems || ne > cap_elems))) return set_err(op, FW_ERR_CAPACITY, "output too small");
+  if (op->join && nr)  // (idempotent: the join stage may have done it already)
+    hipLaunchKernelGGL(k_join_first, dim3(grid_for(nr)), dim3(256), 0, op->stream, op->S, nr);
   const int64_t* src[] = {op->S.rkey, op->S.rstart, op->S.rend, op->S.rcnt, op->S.rsum, op->S.rmin, op->S.rmax,
                           op->S.rfirst, op->S.roff};
   int64_t* dst[] = {rows->key, rows->start, rows->end, rows->count, rows->sum, rows->min, rows->max, rows->first,
@@ -2670,6 +3059,7 @@ int fw_list_drain(fw_list* op, const fw_list_rows* rows, int64_t cap_rows, const
   LHIP(op, hipStreamSynchronize(op->stream));
   op->fired_total += nr;
   op->h_ctr->rows = op->h_ctr->elems = 0;
+  op->j_rows = op->j_elems = -1;
   return FW_OK;
 }
 
@@ -2681,6 +3071,7 @@ int fw_list_clear_pending(fw_list* op) {
   LHIP(op, hipMemsetAsync(&op->S.ctr->rows, 0, 16, op->stream));  // rows, elems
   LHIP(op, hipStreamSynchronize(op->stream));
   op->h_ctr->rows = op->h_ctr->elems = 0;
+  op->j_rows = op->j_elems = -1;
   return FW_OK;
 }
 
@@ -2837,7 +3228,7 @@ int fw_list_restore_key_group(fw_list* op, int32_t key_group, const fw_list_stat
     }
   }
   if (total != n_elems) return set_err(op, FW_ERR_ARG, "list lengths do not add up to n_elems");
-  for (int64_t i = 0; i < n_elems; i++) max_ord = std::max(max_ord, src->ordinal[i]);
+  for (int64_t i = 0; i < n_elems; i++) max_ord = std::max(max_ord, (int64_t)(src->ordinal[i] & ~FW_ORD_SIDE));
   LRET(read_ctr(op));
   if ((int64_t)op->h_ctr->live_groups + n_lists > op->gcap / 2) LRET(compact(op, (int64_t)op->h_ctr->live_groups + n_lists));
   LRET(grow_log(op, n_elems));
@@ -2990,7 +3381,7 @@ int fw_list_restore_sessions(fw_list* op, int32_t key_group, const fw_session_st
       return set_err(op, FW_ERR_KEY_GROUP, "key %lld is not in key group %d", (long long)src->key[i], key_group);
   }
   if (total != n_elems) return set_err(op, FW_ERR_ARG, "list lengths do not add up to n_elems");
-  for (int64_t i = 0; i < n_elems; i++) max_ord = std::max(max_ord, src->ordinal[i]);
+  for (int64_t i = 0; i < n_elems; i++) max_ord = std::max(max_ord, (int64_t)(src->ordinal[i] & ~FW_ORD_SIDE));
   {  // per key: the windows pairwise non-intersecting (TimeWindow.intersects), the state windows distinct
     std::vector<int64_t> ix((size_t)nw);
     for (int64_t i = 0; i < nw; i++) ix[(size_t)i] = i;

@@ -819,8 +819,11 @@ def fire_times_from_heap(fire_mappings):
     return {(key, window): int(f) for window, key, f in fire_mappings}
 
 
+FW_ORD_SIDE = 1 << 62  # a join handle's element: its input in bit 62 of the ordinal (include/flink_window.h)
+
+
 def list_state_from_heap(mappings, timers, key_id, value_of, ts_of=None, ordinal_base=0, trigger_counts=None,
-                         fire_times=None):
+                         fire_times=None, side_of=None):
     """A window-contents ListState (WindowOperator: the values; EvictingWindowOperator: StreamRecords) as the list
     operator's state: (lists [dict key, start, end, trigger_count, timer, n_elems], elements [(ts, val, ordinal)]).
     Values without a timestamp get Long.MIN_VALUE ("no timestamp").  trigger_counts: a CountTrigger's counts
@@ -828,7 +831,10 @@ def list_state_from_heap(mappings, timers, key_id, value_of, ts_of=None, ordinal
     EventTimeTrigger operators (the list operator refuses nothing here: the caller knows its trigger).
     fire_times: a ContinuousEventTimeTrigger's fire times (fire_times_from_heap) instead: the trigger_count column
     then carries a window's fire time, Long.MIN_VALUE when it has none, and timer gains bit 2 when the timer at that
-    fire time is among `timers` (fw_list_state, include/flink_window.h)."""
+    fire time is among `timers` (fw_list_state, include/flink_window.h).
+    side_of: a window join's state (the values are TaggedUnions, CoGroupedStreams.java:273-304): side_of(value) is 0
+    for input 1 and 1 for input 2, and the ordinal carries it in FW_ORD_SIDE as a join handle's restore expects; on
+    the way back (heap_from_list_state) make_value reads it from the element's ordinal."""
     lists, elems = [], []
     o = ordinal_base
     for (start, end), key, values in mappings:
@@ -840,7 +846,8 @@ def list_state_from_heap(mappings, timers, key_id, value_of, ts_of=None, ordinal
         lists.append(dict(key=key_id(key), start=start, end=end, trigger_count=tc, timer=timer, n_elems=len(values)))
         for v in values:
             ts = ts_of(v) if ts_of else None
-            elems.append((-(1 << 63) if ts is None else ts, value_of(v), o))
+            elems.append((-(1 << 63) if ts is None else ts, value_of(v),
+                          o | (FW_ORD_SIDE if side_of is not None and side_of(v) else 0)))
             o += 1
     return lists, elems
 
@@ -858,7 +865,7 @@ def heap_from_list_state(lists, elems, key_name, make_value):
 
 # ---------------------------------------------------------------- session windows: MergingWindowSet form
 def session_state_from_heap(contents, mapping, timers, key_id, value_of, ts_of=None, ordinal_base=0, counts=None,
-                            fire_times=None):
+                            fire_times=None, side_of=None):
     """A merging WindowOperator's keyed state as the list operator's session state (fw_session_state): (windows
     [dict key, start, end, state_start, state_end, trigger_state, timer, n_elems], elements [(ts, val, ordinal)]).
     contents: "window-contents" [(state window, key, values)]; mapping: "merging-window-set" [(VoidNamespace, key,
@@ -866,7 +873,8 @@ def session_state_from_heap(contents, mapping, timers, key_id, value_of, ts_of=N
     (trigger_counts_from_heap) or fire_times: ContinuousEventTimeTrigger's (fire_times_from_heap) -- the trigger's
     state is kept under the actual window, the list under the state window, and a purged window exists in the mapping
     only.  timer bit 1: the window's maxTimestamp timer is among `timers` and is not its cleanup timer's only reason
-    (under CountTrigger no trigger timer exists: the bit stays 0); bit 2: the timer at the fire time is."""
+    (under CountTrigger no trigger timer exists: the bit stays 0); bit 2: the timer at the fire time is.
+    side_of: as list_state_from_heap (a window join over session windows)."""
     lists = {(key, tuple(sw)): values for sw, key, values in contents}
     wins, elems = [], []
     o = ordinal_base
@@ -886,7 +894,8 @@ def session_state_from_heap(contents, mapping, timers, key_id, value_of, ts_of=N
                              state_end=state[1], trigger_state=ts_state, timer=timer, n_elems=len(values)))
             for v in values:
                 ts = ts_of(v) if ts_of else None
-                elems.append((-(1 << 63) if ts is None else ts, value_of(v), o))
+                elems.append((-(1 << 63) if ts is None else ts, value_of(v),
+                              o | (FW_ORD_SIDE if side_of is not None and side_of(v) else 0)))
                 o += 1
     return wins, elems
 

@@ -41,7 +41,7 @@ class GpuListWindowOperator:
     def __init__(self, assigner: WindowAssigner, trigger: Trigger = None, evictor: Evictor = None,
                  allowed_lateness=0, side_output=False, value_type="long", key_type="long", max_parallelism=128,
                  key_group_range: KeyGroupRange = None, emit_contents=True, window_function=None, device=0,
-                 expected_elements=0, max_batch=0, merging_state=False):
+                 expected_elements=0, max_batch=0, merging_state=False, join=0, max_join_pairs=0):
         trigger = trigger or EventTimeTrigger.create()
         nested = getattr(trigger, "nested", trigger)
         if not isinstance(nested, (EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger)):
@@ -83,7 +83,11 @@ class GpuListWindowOperator:
         self._cfg = c
         self._h = ctypes.c_void_p()
         L = N.lib()
-        rc = L.fw_list_create(ctypes.byref(c), ctypes.byref(self._h))
+        if join:  # (flink_amd.join.GpuWindowJoin: the operator over the tagged union of two inputs)
+            jc = N.FwJoinConfig(join=int(join), max_join_pairs=int(max_join_pairs))
+            rc = L.fw_list_create_join(ctypes.byref(c), ctypes.byref(jc), ctypes.byref(self._h))
+        else:
+            rc = L.fw_list_create(ctypes.byref(c), ctypes.byref(self._h))
         if rc != N.FW_OK:
             msg = L.fw_list_last_error(self._h).decode() if self._h else "fw_list_create failed"
             L.fw_list_destroy(self._h)
@@ -107,10 +111,13 @@ class GpuListWindowOperator:
             raise N.NativeError(rc, N.lib().fw_list_last_error(self._h).decode())
 
     # ------------------------------------------------------------------ processElement
-    def process_batch(self, keys, timestamps, values, key_hash=None):
+    def process_batch(self, keys, timestamps, values, key_hash=None, side=None):
         """processElement for every record of the batch, in order; rows fired meanwhile (count triggers, late
-        firings) are kept for the next drain."""
+        firings) are kept for the next drain.  side (join handles): the batch's input, 0 or 1."""
         L = N.lib()
+        tag = () if side is None else (int(side),)
+        push_device = L.fw_list_push_batch_device if side is None else L.fw_list_push_batch_side_device
+        push_host = L.fw_list_push_batch if side is None else L.fw_list_push_batch_side
         fl = self.value_type in ("double", "float")
         if _is_torch(keys):
             import torch
@@ -122,8 +129,8 @@ class GpuListWindowOperator:
             if keys.dtype != torch.int64 or timestamps.dtype != torch.int64 or values.dtype != want:
                 raise ValueError(f"keys / timestamps must be int64 and values {want}")
             torch.cuda.current_stream(keys.device).synchronize()  # the push reads the columns on its own stream
-            rc = L.fw_list_push_batch_device(self._h, keys.data_ptr(), timestamps.data_ptr(), values.data_ptr(),
-                                             key_hash.data_ptr() if key_hash is not None else None, n)
+            rc = push_device(self._h, *tag, keys.data_ptr(), timestamps.data_ptr(), values.data_ptr(),
+                             key_hash.data_ptr() if key_hash is not None else None, n)
         else:
             keys = np.ascontiguousarray(keys, dtype=np.int64)
             timestamps = np.ascontiguousarray(timestamps, dtype=np.int64)
@@ -134,8 +141,7 @@ class GpuListWindowOperator:
                 kh = key_hash.ctypes.data
             if not (len(keys) == len(timestamps) == len(values)):
                 raise ValueError("columns must have equal length")
-            rc = L.fw_list_push_batch(self._h, keys.ctypes.data, timestamps.ctypes.data, values.ctypes.data, kh,
-                                      len(keys))
+            rc = push_host(self._h, *tag, keys.ctypes.data, timestamps.ctypes.data, values.ctypes.data, kh, len(keys))
         self._check(rc)
 
     processElements = process_batch

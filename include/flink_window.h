@@ -764,6 +764,76 @@ int fw_list_snapshot_sessions(fw_list* op, int32_t key_group, const fw_session_s
 int fw_list_restore_sessions(fw_list* op, int32_t key_group, const fw_session_state* src, int64_t n_windows,
                              int64_t n_elems);
 
+/* ---- window joins: DataStream.join(other).where().equalTo().window().apply(JoinFunction) and coGroup(...).
+ * In the reference a window join is not an operator of its own.  CoGroupedStreams.WithWindow.apply
+ * (flink-streaming-java .../api/datastream/CoGroupedStreams.java:273-304) tags both inputs (Input1Tagger /
+ * Input2Tagger, TaggedUnion), unions and keys them, and builds the ordinary WindowOperator / EvictingWindowOperator
+ * over a ListState with the user's assigner, trigger and evictor.  CoGroupWindowFunction.apply (:657-685) splits every
+ * firing's contents by tag into two lists, each in list order, and JoinedStreams' JoinCoGroupFunction.coGroup
+ * (JoinedStreams.java:387-404) collects join(val1, val2) for every val1 of the first list and, inside, every val2 of
+ * the second.  WithWindow passes no allowed lateness.
+ *
+ * A handle created by fw_list_create_join with fw_join_config::join != 0 is that operator: every assigner, trigger, evictor, lateness,
+ * side-output and merging_state combination of the list operator, and emit_contents = 1 (FW_ERR_ARG otherwise: the
+ * join reads the contents).  Its elements carry their input as bit 62 of the arrival ordinal (FW_ORD_SIDE: set = input
+ * 2).  Every ordinal column that leaves the handle carries the bit -- the elements of fw_list_drain and
+ * fw_list_drain_join, fw_list_state and fw_session_state snapshots -- and a restore takes it back in (later pushes are
+ * numbered after the largest restored ordinal with the bit cleared); the rows' `first` column is the plain ordinal,
+ * bit cleared.  fw_list_push_batch_side(_device) push a batch of one input (side 0 = input 1, 1 = input 2; one batch
+ * comes from one input, as the union delivers buffers); fw_list_push_batch(_device) on a join handle mean input 1.  A
+ * side push on a handle without a join, or a side outside {0, 1}, is FW_ERR_ARG.  The side output of a join handle
+ * carries key, ts and val as on every handle: the side of a late record is not reported (the reference's side output
+ * would carry the TaggedUnion).
+ *
+ * The join stage is a function of the pending output alone (the fired rows and their elements); it runs when one of the
+ * three calls below asks for it and never touches the operator's state, so a refusal leaves everything as it was.
+ *   split   per fired row n_first = its elements of input 1, and a partitioned copy of its elements: those of input 1
+ *           in list order, then those of input 2 in list order (CoGroupWindowFunction's two lists), at the row's
+ *           elem_off.  fw_list_drain keeps returning the unpartitioned list order.
+ *   count   pairs of a row = n_first * (count - n_first) (64 bits), 0 on a FW_JOIN_COGROUP handle.
+ *   emit    (FW_JOIN_INNER) pair q of a row is (i, j) = (q / n2, q % n2), i-major -- JoinCoGroupFunction's order --,
+ *           a row's pairs contiguous and rows in row order; SoA int64 columns: row = the index of the fired row among
+ *           the drained rows, idx1 / idx2 = the indices of the two elements among the drained partitioned elements
+ *           (a consumer gathers ts, value or ordinal through them: a JoinFunction other than the projection is the
+ *           host's), val1 / val2 = the two value fields, the built-in join(a, b) = (a.field, b.field) (double bits
+ *           for FW_VAL_F64 / FW_VAL_F32).
+ * fw_list_join_pending runs split and count: the pending rows, elements and (exactly, also beyond what any buffer
+ * holds) pairs.  fw_list_drain_join copies all pending rows, n_first, the partitioned elements and the pairs to the
+ * host and clears them, or drains nothing: FW_ERR_CAPACITY with the three counts set when a capacity is too small; a
+ * NULL column is skipped; pairs == NULL drains the coGroup form alone and materialises no pair.  More pending pairs
+ * than max_join_pairs are not materialised (FW_ERR_CAPACITY, nothing changed; drain with pairs == NULL, or drain more
+ * often).  fw_list_join_device fills the structs with device pointers, valid until the next call on the handle, and
+ * clears nothing (fw_list_clear_pending does; pairs == NULL: no pairs).  All three return FW_ERR_ARG on a handle
+ * without a join, which allocates and launches nothing of this. */
+#define FW_JOIN_NONE 0
+#define FW_JOIN_COGROUP 1
+#define FW_JOIN_INNER 2
+#define FW_ORD_SIDE (1LL << 62)
+/* the join of a handle, given to fw_list_create_join beside the list operator's configuration (fw_list_config keeps its
+ * layout: a handle made by fw_list_create has no join) */
+typedef struct fw_join_config {
+  int32_t join;              /* FW_JOIN_COGROUP or FW_JOIN_INNER; FW_JOIN_NONE = what fw_list_create makes            */
+  int32_t pad;
+  int64_t max_join_pairs;    /* FW_JOIN_INNER: the most pending pairs fw_list_drain_join / fw_list_join_device
+                                materialise (0 = 2^30, 40 GB of columns); >= 0                                     */
+} fw_join_config;
+typedef struct fw_join_pairs {
+  int64_t *row, *idx1, *idx2, *val1, *val2;
+} fw_join_pairs;
+/* fw_list_create with a join.  Refused before the device is touched, beside fw_list_create's own refusals: join outside
+ * 0..2, join != 0 with emit_contents == 0, max_join_pairs < 0 (FW_ERR_ARG).  join NULL or join->join == 0: fw_list_create */
+int fw_list_create_join(const fw_list_config* cfg, const fw_join_config* join, fw_list** out);
+int fw_list_push_batch_side(fw_list* op, int32_t side, const int64_t* key, const int64_t* ts, const void* val,
+                            const int32_t* key_hash, int64_t n);
+int fw_list_push_batch_side_device(fw_list* op, int32_t side, const int64_t* key, const int64_t* ts, const void* val,
+                                   const int32_t* key_hash, int64_t n);
+int fw_list_join_pending(fw_list* op, int64_t* n_rows, int64_t* n_elems, int64_t* n_pairs);
+int fw_list_drain_join(fw_list* op, const fw_list_rows* rows, int64_t* n_first, int64_t cap_rows,
+                       const fw_list_elems* elems, int64_t cap_elems, const fw_join_pairs* pairs, int64_t cap_pairs,
+                       int64_t* n_rows, int64_t* n_elems, int64_t* n_pairs);
+int fw_list_join_device(fw_list* op, fw_list_rows* rows, int64_t** n_first, fw_list_elems* elems, fw_join_pairs* pairs,
+                        int64_t* n_rows, int64_t* n_elems, int64_t* n_pairs);
+
 /* Count windows (an fw_op with FW_COUNT): the keyed state of one key group, in the logical form of the list operator
  * above, so it moves between count handles of any parallelism and to and from the equivalent fw_list handle
  * (FW_GLOBAL, FW_TRIGGER_COUNT with trigger_count = slide, FW_EVICT_COUNT with evict_count = size and the same
