@@ -8,7 +8,7 @@ from .keygroups import (KeyGroupRange, assign_key_to_parallel_operator, assign_t
                         compute_default_max_parallelism, compute_key_group_range_for_operator_index,
                         compute_operator_index_for_key_group, long_hash_code, murmur_hash, string_hash_code)
 from .windowing import (ContinuousEventTimeTrigger, CountEvictor, CountTrigger, DeltaEvictor, GlobalWindows,  # noqa: F401
-                        TimeEvictor,
+                        DeltaTrigger, TimeEvictor,
                         CountSumMinMax, CountWindows, ExtremalElementReduce, FirstElementReduce, HyperLogLog, TDigest,  # noqa: F401
                         RowAggregate,
                         EventTimeSessionWindows, EventTimeTrigger, PurgingTrigger, SlidingEventTimeWindows, Time,

@@ -98,7 +98,7 @@ class FwWireStats(ctypes.Structure):
 
 
 FW_GLOBAL = 4
-FW_TRIGGER_EVENT_TIME, FW_TRIGGER_COUNT, FW_TRIGGER_CONTINUOUS_EVENT_TIME = 0, 1, 2
+FW_TRIGGER_EVENT_TIME, FW_TRIGGER_COUNT, FW_TRIGGER_CONTINUOUS_EVENT_TIME, FW_TRIGGER_DELTA = 0, 1, 2, 3
 FW_EVICT_NONE, FW_EVICT_COUNT, FW_EVICT_TIME, FW_EVICT_DELTA = 0, 1, 2, 3
 
 
@@ -110,6 +110,16 @@ class FwListConfig(ctypes.Structure):
                                        "evict_count")] + \
         [("delta_threshold", ctypes.c_double), ("expected_elements", ctypes.c_int64), ("max_batch", ctypes.c_int64),
          ("trigger_interval", ctypes.c_int64)]
+
+    # fw_list_config's last slot is a union: ContinuousEventTimeTrigger's trigger_interval or, for FW_TRIGGER_DELTA,
+    # DeltaTrigger's trigger_threshold (a double in the same eight bytes)
+    @property
+    def trigger_threshold(self):
+        return ctypes.c_double.from_buffer_copy(ctypes.c_int64(self.trigger_interval)).value
+
+    @trigger_threshold.setter
+    def trigger_threshold(self, x):
+        self.trigger_interval = ctypes.c_int64.from_buffer_copy(ctypes.c_double(x)).value
 
 
 FW_JOIN_NONE, FW_JOIN_COGROUP, FW_JOIN_INNER = 0, 1, 2

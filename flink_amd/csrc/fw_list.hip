@@ -3,7 +3,8 @@
 // (paths relative to /root/reference/flink-streaming-java/src/main/java/org/apache/flink/streaming/):
 //   runtime/operators/windowing/EvictingWindowOperator.java:102-239 processElement, :241-286 onEventTime,
 //   :334-366 emitWindowContents; WindowOperator.java:291-469 (no evictor), :576-651 lateness and cleanup;
-//   api/windowing/triggers/{EventTimeTrigger.java:37-73, CountTrigger.java:47-70, PurgingTrigger.java:45-59};
+//   api/windowing/triggers/{EventTimeTrigger.java:37-73, CountTrigger.java:47-70, PurgingTrigger.java:45-59,
+//   DeltaTrigger.java:38-99};
 //   api/windowing/evictors/{CountEvictor.java:50-78, TimeEvictor.java:54-104, DeltaEvictor.java:59-80}.
 //
 // HBM layout (one handle = one subtask on one GPU):
@@ -23,6 +24,8 @@
 // same way, and drops the cleaned-up ones.
 // ContinuousEventTimeTrigger (triggers/ContinuousEventTimeTrigger.java:39-151) adds a fire time per group (gfire) and
 // a second timer: a watermark then fires a list once per due timer ("ContinuousEventTimeTrigger" below).
+// DeltaTrigger keeps a last element per group (its value bits in gfire's column, GF_LAST = present) and fires only
+// while elements are processed ("DeltaTrigger" below): every push of such a handle takes the ordered walk.
 // Window joins (fw_list_create_join; "window joins" below): the same operator over the tagged union of two inputs, an
 // element's input in bit 62 of its ordinal, and a stage over the pending output that splits every firing by input and
 // forms the pairs (CoGroupedStreams.java:273-304, :657-685; JoinedStreams.java:387-404).
@@ -52,7 +55,8 @@ constexpr int64_t LMIN = INT64_MIN;
 #define FW_LIST_ROOM (int64_t(1) << 28)  // elements a walk may size its output for up front
 #endif
 // GF_FPEND: ContinuousEventTimeTrigger's timer at the window's fire time is registered
-enum : uint32_t { GF_TIMER = 1u, GF_TOUCH = 2u, GF_FIRE = 4u, GF_CLEAN = 8u, GF_FPEND = 16u };
+// GF_LAST: DeltaTrigger's "last-element" ValueState is present (its value bits: gfire[])
+enum : uint32_t { GF_TIMER = 1u, GF_TOUCH = 2u, GF_FIRE = 4u, GF_CLEAN = 8u, GF_FPEND = 16u, GF_LAST = 32u };
 constexpr unsigned long long CF_MAX_FIRINGS = 1ull << 20;  // of one window in one watermark advance
 enum : uint32_t {
   LF_NO_TS = 1u, LF_KEY_GROUP = 2u, LF_MAP_FULL = 4u, LF_ELEMS = 8u, LF_MERGE_LATE = 16u, LF_MERGE_WIDE = 32u,
@@ -69,7 +73,10 @@ struct LCfg {
   int32_t assigner, vt, key_kind, trigger, purging, evictor, evict_after, side_output, emit, max_par, kg0, nkg;
   int64_t size, slide, offset, lateness, trig_n, ev_n;
   double thr;
-  int64_t trig_i;  // ContinuousEventTimeTrigger's interval
+  union {
+    int64_t trig_i;   // ContinuousEventTimeTrigger's interval
+    double trig_thr;  // DeltaTrigger's threshold
+  };
   int64_t wcap;    // sliding: the most windows of a record, ceil(size / slide) + 1 (a displaced record's extra one)
 };
 
@@ -96,8 +103,9 @@ struct alignas(32) LPay {
 struct LState {
   GSlot* g;  // the group map: one 32-byte slot per group (a lookup reads one sector)
   uint32_t gmask;
-  // ContinuousEventTimeTrigger only (null otherwise): per slot the trigger's "fire-time" state (LMIN = null), and
-  // for the time / global windows a scratch (all ones between pushes) for the first arming element of a push
+  // The triggers with 8 bytes of partitioned state per window (null otherwise).  ContinuousEventTimeTrigger: the
+  // "fire-time" state (LMIN = null), and for the time / global windows a scratch gfpos (all ones between pushes) for
+  // the first arming element of a push.  DeltaTrigger: the value bits of "last-element" (valid with GF_LAST; no gfpos)
   int64_t* gfire;
   uint32_t* gfpos;
   // session windows (FW_SESSION, fw_list.hip "session windows"): per slot its window end and list head / tail
@@ -299,8 +307,10 @@ __global__ __launch_bounds__(256) void k_lp_append(LCfg c, LState S, const int64
       return;
     }
     const int64_t mts = w_max_ts(c, s);
-    due = min(due, (long long)(c.trigger != FW_TRIGGER_COUNT && mts > wm ? mts : w_cleanup(c, s)));
-    if (c.trigger == FW_TRIGGER_COUNT || mts <= wm) {  // CountTrigger / late firing
+    // (CountTrigger and DeltaTrigger register no timer and decide per element: FW_TRIGGER_COUNT | 2 = FW_TRIGGER_DELTA)
+    const bool per_elem = (c.trigger | 2) == FW_TRIGGER_DELTA;
+    due = min(due, (long long)(!per_elem && mts > wm ? mts : w_cleanup(c, s)));
+    if (per_elem || mts <= wm) {  // CountTrigger / DeltaTrigger / late firing
       atomicOr(&S.g[g].fl, GF_TOUCH);
       seq = true;
     } else if (!(fl & GF_TIMER)) {  // EventTimeTrigger.onElement registers the timer at maxTimestamp
@@ -680,6 +690,82 @@ __global__ __launch_bounds__(256) void k_walk_bound(LCfg c, LState S, const uint
     for (int64_t q = a; q < b; q++) nn += (int64_t)pos[q] >= base_new;
     const int64_t f = c.trigger == FW_TRIGGER_COUNT ? (S.g[keys[a]].cnt + nn) / max<int64_t>(1, c.trig_n) : nn;
     tot += (unsigned long long)(f * (b - a));
+  }
+  if (tot) atomicAdd(&S.ctr->count, tot);
+}
+
+// ---------------------------------------------------------------- DeltaTrigger
+// DeltaTrigger.onElement (DeltaTrigger.java:53-64) with the built-in DeltaFunction getDelta(old, new) = new.field -
+// old.field, the mirror of the DeltaEvictor's (delta_of): no "last-element" state -> the element is stored, CONTINUE;
+// delta > threshold (strict; a NaN delta compares false) -> the element is stored, FIRE; else CONTINUE.  The state
+// (GF_LAST, gfire[]) is the group's: a purge or an eviction leaves it, k_rebuild_map carries it, the cleanup
+// drops it with the group (clearAllState -> Trigger.clear).  onEventTime is CONTINUE and no timer is registered, so
+// a watermark has only cleanups to do (k_lw_due: GF_TIMER is never set) and every firing happens here, in a push.
+__device__ __forceinline__ bool dt_fires(const LCfg& c, int64_t last, int64_t v) {
+  return delta_of(c, last, v) > c.trig_thr;
+}
+// k_walk<true>'s walk for a DeltaTrigger handle: one thread per touched list, its new elements in order.  The state
+// is advanced in registers and stored once the walk of the list ends or stops; an element takes the place of the
+// last one only after its firing has its room (emit_firing returned true), so a walk that stopped on a full element
+// buffer at element j (prog[s] = j) is launched again with the state as it was before j and decides j the same way.
+__global__ __launch_bounds__(256) void k_walk_delta(LCfg c, LState S, LView V, const uint32_t* __restrict__ keys,
+                                                    const uint32_t* __restrict__ seg, int64_t nseg, int64_t base_new,
+                                                    int64_t* __restrict__ prog, bool room) {
+  const uint32_t* __restrict__ pos = V.pos;
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nseg; s += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t a = seg[s], b = seg[s + 1];
+    const uint32_t g = keys[a];
+    const uint32_t fl = S.g[g].fl;
+    if (!(fl & GF_TOUCH)) continue;
+    int64_t j = prog[s] >= 0 ? prog[s] : a;
+    while (j < b && (int64_t)pos[j] < base_new) j++;
+    bool have = (fl & GF_LAST) != 0, stopped = false;
+    int64_t last = have ? S.gfire[g] : 0;
+    for (; j < b; j++) {
+      const int64_t v = V.val[j];
+      if (have) {
+        if (!dt_fires(c, last, v)) continue;
+        if (!emit_firing(c, S, V, g, a, j, room)) {
+          prog[s] = j;
+          stopped = true;
+          break;
+        }
+        if (c.purging) purge(S, V, a, j);
+      }
+      last = v;  // lastElementState.update(element)
+      have = true;
+    }
+    if (have) {
+      S.gfire[g] = last;
+      if (!(fl & GF_LAST)) atomicOr(&S.g[g].fl, GF_LAST);
+    }
+    if (!stopped) atomicAnd(&S.g[g].fl, ~GF_TOUCH);
+  }
+}
+// The elements k_walk_delta can emit, exactly as many firings as it will make: whether an element fires depends on
+// the values and the stored state alone, not on what evictors or purges removed, so the same recurrence runs here
+// over the new elements' values (read through the log: the view is not gathered yet) and every firing is charged
+// the list up to its element (what it emits unless an evictor or a purge made it shorter).
+__global__ __launch_bounds__(256) void k_walk_bound_delta(LCfg c, LState S, const uint32_t* __restrict__ pos,
+                                                          const uint32_t* __restrict__ keys,
+                                                          const uint32_t* __restrict__ seg, int64_t nseg,
+                                                          int64_t base_new) {
+  unsigned long long tot = 0;
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nseg; s += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t a = seg[s], b = seg[s + 1];
+    const uint32_t g = keys[a];
+    bool have = (S.g[g].fl & GF_LAST) != 0;
+    int64_t last = have ? S.gfire[g] : 0;
+    for (int64_t q = a; q < b; q++) {
+      if ((int64_t)pos[q] < base_new) continue;
+      const int64_t v = S.lpay[pos[q]].val;
+      if (have) {
+        if (!dt_fires(c, last, v)) continue;
+        tot += (unsigned long long)(q - a + 1);
+      }
+      last = v;
+      have = true;
+    }
   }
   if (tot) atomicAdd(&S.ctr->count, tot);
 }
@@ -1064,6 +1150,14 @@ __global__ void k_restore_groups(LCfg c, LState S, const int64_t* __restrict__ k
     if (ins) atomicAdd(&S.ctr->live_groups, 1ull);  // (one thread)
     gid_out[i] = g;
     if (g < 0) continue;
+    if (c.trigger == FW_TRIGGER_DELTA) {  // the count column is the last element's value bits, timer bit 4 = present
+      if (timer[i] & 4) {
+        S.gfire[g] = cnt[i];
+        atomicOr(&S.g[g].fl, GF_LAST);
+      }
+      atomicMin(&S.ctr->next_due, (long long)w_cleanup(c, start[i]));
+      continue;
+    }
     if (S.gfire) {  // ContinuousEventTimeTrigger: the count column is the fire time, timer its two registrations
       if (cnt[i] != LMIN) S.gfire[g] = S.gfire[g] == LMIN ? cnt[i] : min(S.gfire[g], cnt[i]);
       atomicOr(&S.g[g].fl, ((timer[i] & 1) ? GF_TIMER : 0u) | ((timer[i] & 2) && cnt[i] != LMIN ? GF_FPEND : 0u));
@@ -2052,6 +2146,7 @@ int alloc_map(fw_list* op, LState& S, int64_t cap) {
   S.gmask = (uint32_t)(cap - 1);
   S.gfire = nullptr;
   S.gfpos = nullptr;
+  if (op->c.trigger == FW_TRIGGER_DELTA) LHIP(op, dmalloc(&S.gfire, (size_t)cap));  // (read only under GF_LAST)
   if (op->c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME) {  // every slot's fire time null
     LHIP(op, dmalloc(&S.gfire, (size_t)cap));
     hipLaunchKernelGGL(k_fill64, dim3(grid_for(cap)), dim3(256), 0, op->stream, S.gfire, cap, LMIN);
@@ -2188,12 +2283,17 @@ int walk_lists(fw_list* op, uint32_t bit, int64_t base_new) {
   // FW_LIST_ROOM elements) it reserves with compare-and-swap and stops where the buffer is full
   // a ContinuousEventTimeTrigger watermark: a list fires once per due timer (k_walk_cf)
   const bool cf = !PUSH && op->c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME;
+  // a DeltaTrigger push: the firings follow the values (k_walk_delta), and the bound counts them exactly
+  const bool dt = PUSH && op->c.trigger == FW_TRIGGER_DELTA;
   bool room = !op->c.emit;
   if (op->c.emit) {
     LHIP(op, hipMemsetAsync(&op->S.ctr->count, 0, 8, op->stream));
     if (cf)
       hipLaunchKernelGGL(k_walk_bound_cf, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, op->keys2,
                          op->seg, nseg, op->wm);
+    else if (dt)
+      hipLaunchKernelGGL(k_walk_bound_delta, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, op->sel2,
+                         op->keys2, op->seg, nseg, base_new);
     else
       hipLaunchKernelGGL(k_walk_bound<PUSH>, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, op->sel2,
                          op->keys2, op->seg, nseg, base_new);
@@ -2224,6 +2324,9 @@ int walk_lists(fw_list* op, uint32_t bit, int64_t base_new) {
     if (cf)
       hipLaunchKernelGGL(k_walk_cf, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, V, op->keys2, op->seg,
                          nseg, op->wm, room);
+    else if (dt)
+      hipLaunchKernelGGL(k_walk_delta, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, V, op->keys2,
+                         op->seg, nseg, base_new, op->prog, room);
     else
       hipLaunchKernelGGL(k_walk<PUSH>, dim3(grid_for(nseg)), dim3(256), 0, op->stream, op->c, op->S, V, op->keys2,
                          op->seg, nseg, base_new, op->wm, op->prog, room);
@@ -2805,6 +2908,8 @@ int fw_list_create_join(const fw_list_config* cfg, const fw_join_config* jcfg, f
     return fail(FW_ERR_ARG, "EventTimeSessionWindows parameters must satisfy 0 < size");
   if (c.merging_state != 0 && (c.merging_state != 1 || c.assigner != FW_SESSION))
     return fail(FW_ERR_ARG, "merging_state is 0 or 1, and 1 only with FW_SESSION");
+  if (c.assigner == FW_SESSION && c.trigger == FW_TRIGGER_DELTA)  // WindowedStream.trigger: DeltaTrigger has no canMerge
+    return fail(FW_ERR_ARG, "A merging window assigner cannot be used with a trigger that does not support merging.");
   if (c.assigner == FW_SESSION && !c.merging_state && c.trigger != FW_TRIGGER_EVENT_TIME &&
       c.trigger != FW_TRIGGER_CONTINUOUS_EVENT_TIME)
     return fail(FW_ERR_UNSUPPORTED, "session windows over ListState are offered with EventTimeTrigger or "
@@ -2815,8 +2920,11 @@ int fw_list_create_join(const fw_list_config* cfg, const fw_join_config* jcfg, f
   if (c.assigner == FW_SLIDING && (c.size <= 0 || c.slide <= 0 || c.slide > c.size || c.offset < 0 || c.offset >= c.slide))
     return fail(FW_ERR_ARG, "SlidingEventTimeWindows parameters must satisfy 0 <= offset < slide <= size");
   if (c.allowed_lateness < 0) return fail(FW_ERR_ARG, "The allowed lateness cannot be negative.");
-  if (c.trigger != FW_TRIGGER_EVENT_TIME && c.trigger != FW_TRIGGER_COUNT && c.trigger != FW_TRIGGER_CONTINUOUS_EVENT_TIME)
+  if (c.trigger != FW_TRIGGER_EVENT_TIME && c.trigger != FW_TRIGGER_COUNT &&
+      c.trigger != FW_TRIGGER_CONTINUOUS_EVENT_TIME && c.trigger != FW_TRIGGER_DELTA)
     return fail(FW_ERR_ARG, "unknown trigger");
+  if (c.trigger == FW_TRIGGER_DELTA && c.trigger_threshold != c.trigger_threshold)
+    return fail(FW_ERR_ARG, "DeltaTrigger threshold must not be NaN");
   if (c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME && c.trigger_interval <= 0)
     return fail(FW_ERR_ARG, "ContinuousEventTimeTrigger interval must be > 0");
   if (c.trigger == FW_TRIGGER_COUNT && (c.trigger_count <= 0 || c.trigger_count > INT32_MAX))
@@ -2831,6 +2939,9 @@ int fw_list_create_join(const fw_list_config* cfg, const fw_join_config* jcfg, f
   if (jc.join != FW_JOIN_NONE && !c.emit_contents)
     return fail(FW_ERR_ARG, "a window join reads the contents of every firing: emit_contents must be 1");
   if (jc.max_join_pairs < 0) return fail(FW_ERR_ARG, "max_join_pairs must be >= 0");
+  if (jc.join != FW_JOIN_NONE && c.trigger == FW_TRIGGER_DELTA)
+    return fail(FW_ERR_UNSUPPORTED, "a window join does not take DeltaTrigger: a DeltaFunction over the tagged union "
+                                    "of the two inputs is user code");
   op->join = jc.join;
   op->max_pairs = jc.max_join_pairs > 0 ? jc.max_join_pairs : int64_t(1) << 30;
   const int32_t mp = c.max_parallelism ? c.max_parallelism : 128;
@@ -2840,8 +2951,9 @@ int fw_list_create_join(const fw_list_config* cfg, const fw_join_config* jcfg, f
   op->c = LCfg{c.assigner, c.value_type, c.key_kind, c.trigger, c.purging, c.evictor, c.evict_after, c.side_output,
                c.emit_contents, mp, kg0, kg1 - kg0 + 1, c.size, c.slide, c.offset, c.allowed_lateness,
                c.trigger_count, c.evict_count, c.delta_threshold,
-               c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME ? c.trigger_interval : 0,
+               {c.trigger == FW_TRIGGER_CONTINUOUS_EVENT_TIME ? c.trigger_interval : 0},
                c.assigner == FW_SLIDING ? c.size / c.slide + (c.size % c.slide != 0) + 1 : 1};
+  if (c.trigger == FW_TRIGGER_DELTA) op->c.trig_thr = c.trigger_threshold;
   op->device = c.device;
   if (hipSetDevice(c.device) != hipSuccess) return fail(FW_ERR_HIP, "hipSetDevice failed");
   if (hipStreamCreateWithFlags(&op->stream, hipStreamNonBlocking) != hipSuccess)
@@ -3181,6 +3293,17 @@ int fw_list_snapshot_key_group(fw_list* op, int32_t key_group, const fw_list_sta
     LHIP(op, hipMemcpy(&gs, op->S.g + g, sizeof gs, hipMemcpyDeviceToHost));
     const int64_t key = gs.key, start = gs.start, c = gs.cnt;
     const uint32_t fl = gs.fl;
+    if (op->c.trigger == FW_TRIGGER_DELTA) {  // the last element's value bits, timer bit 4 = the state is present
+      int64_t last = 0;
+      if (fl & GF_LAST) LHIP(op, hipMemcpy(&last, op->S.gfire + g, 8, hipMemcpyDeviceToHost));
+      dst->key[i] = key;
+      dst->start[i] = start;
+      dst->end[i] = op->c.assigner == FW_GLOBAL ? LMAX : (int64_t)((uint64_t)start + (uint64_t)op->c.size);
+      dst->trigger_count[i] = last;
+      dst->timer[i] = (fl & GF_LAST) ? 4 : 0;
+      dst->n_elems[i] = cnt[i];
+      continue;
+    }
     if (op->S.gfire) {  // ContinuousEventTimeTrigger: the fire time and the two timers' registrations
       int64_t fire = LMIN;
       LHIP(op, hipMemcpy(&fire, op->S.gfire + g, 8, hipMemcpyDeviceToHost));
@@ -3215,6 +3338,10 @@ int fw_list_restore_key_group(fw_list* op, int32_t key_group, const fw_list_stat
   int64_t total = 0, max_ord = -1;
   for (int64_t i = 0; i < n_lists; i++) {
     if (src->n_elems[i] < 0) return set_err(op, FW_ERR_ARG, "negative list length");
+    // timer bit 4 is DeltaTrigger's "last-element present"; that trigger has no timer (bits 1 and 2)
+    if (op->c.trigger == FW_TRIGGER_DELTA ? (src->timer[i] & ~(int64_t)4) != 0 : (src->timer[i] & 4) != 0)
+      return set_err(op, FW_ERR_ARG, "list %lld: timer bits %lld that the handle's trigger cannot have", (long long)i,
+                     (long long)src->timer[i]);
     total += src->n_elems[i];
     const int64_t s = src->start[i];
     const int64_t e = op->c.assigner == FW_GLOBAL ? LMAX : (int64_t)((uint64_t)s + (uint64_t)op->c.size);

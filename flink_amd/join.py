@@ -27,6 +27,7 @@ import numpy as np
 from . import _native as N
 from .listwindow import LIST_ROW_DTYPE, LIST_ROW_FIELDS, GpuListWindowOperator
 from .operator import ELEM_DTYPE
+from .windowing import DeltaTrigger
 
 PAIR_FIELDS = ("row", "idx1", "idx2", "val1", "val2")
 PAIR_DTYPE = np.dtype([(f, "<i8") for f in ("epoch", "key", "start", "end", "val1", "val2", "ord1", "ord2")])
@@ -47,6 +48,9 @@ class GpuWindowJoin:
                  **list_operator_keywords):
         if mode not in _MODES:
             raise ValueError('mode is "join" or "cogroup"')
+        if isinstance(getattr(trigger, "nested", trigger), DeltaTrigger):
+            raise ValueError("a window join does not take DeltaTrigger: a DeltaFunction over the tagged union of the "
+                             "two inputs is user code")
         kw = dict(list_operator_keywords)
         kw.setdefault("allowed_lateness", 0)
         self.mode = mode

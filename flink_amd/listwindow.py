@@ -7,7 +7,8 @@ with an Iterable window function, and the EvictingWindowOperator (f4; include/fl
   processElement -> process_batch, processWatermark -> process_watermark   (EvictingWindowOperator.java:102-286)
 
 Triggers: EventTimeTrigger, CountTrigger.of(n), ContinuousEventTimeTrigger.of(interval) — early firings, possibly
-several of one window per watermark — each alone or inside PurgingTrigger.
+several of one window per watermark — and DeltaTrigger.of(threshold) over the value field (not over session windows),
+each alone or inside PurgingTrigger.
 
 Session windows keep, by default, only what firing needs.  `merging_state=True` (EventTimeSessionWindows only) makes the
 handle keep the full MergingWindowSet form per in-flight window — its state window and the trigger's count — and with
@@ -26,8 +27,8 @@ import numpy as np
 from . import _native as N
 from .keygroups import KeyGroupRange
 from .operator import ELEM_DTYPE, LIST_STATE_DTYPE, _KEY_KINDS, _is_torch  # (the two dtypes: one definition)
-from .windowing import (VALUE_TYPES, ContinuousEventTimeTrigger, CountTrigger, EventTimeTrigger, Evictor, Trigger,
-                        WindowAssigner)
+from .windowing import (VALUE_TYPES, ContinuousEventTimeTrigger, CountTrigger, DeltaTrigger, EventTimeTrigger, Evictor,
+                        Trigger, WindowAssigner)
 
 LIST_ROW_FIELDS = ("key", "start", "end", "count", "sum", "min", "max", "first", "elem_off")
 LIST_ROW_DTYPE = np.dtype([(f, "<i8") for f in LIST_ROW_FIELDS] + [("epoch", "<i8")])
@@ -44,9 +45,11 @@ class GpuListWindowOperator:
                  expected_elements=0, max_batch=0, merging_state=False, join=0, max_join_pairs=0):
         trigger = trigger or EventTimeTrigger.create()
         nested = getattr(trigger, "nested", trigger)
-        if not isinstance(nested, (EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger)):
-            raise ValueError("triggers: EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger, or PurgingTrigger "
-                             "of one of them")
+        if not isinstance(nested, (EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger, DeltaTrigger)):
+            raise ValueError("triggers: EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger, DeltaTrigger, or "
+                             "PurgingTrigger of one of them")
+        if isinstance(nested, DeltaTrigger) and "gap" in assigner.config():  # WindowedStream.trigger (:136-139)
+            raise ValueError("A merging window assigner cannot be used with a trigger that does not support merging.")
         if allowed_lateness < 0:
             raise ValueError("The allowed lateness cannot be negative.")
         kgr = key_group_range or KeyGroupRange(0, max_parallelism - 1)
@@ -60,8 +63,11 @@ class GpuListWindowOperator:
         c.key_kind = _KEY_KINDS[key_type]
         c.trigger = (N.FW_TRIGGER_COUNT if isinstance(nested, CountTrigger)
                      else N.FW_TRIGGER_CONTINUOUS_EVENT_TIME if isinstance(nested, ContinuousEventTimeTrigger)
+                     else N.FW_TRIGGER_DELTA if isinstance(nested, DeltaTrigger)
                      else N.FW_TRIGGER_EVENT_TIME)
         c.trigger_interval = nested.interval if isinstance(nested, ContinuousEventTimeTrigger) else 0
+        if isinstance(nested, DeltaTrigger):  # (the same slot of fw_list_config: a trigger has one parameter)
+            c.trigger_threshold = nested.threshold
         c.trigger_count = nested.count if isinstance(nested, CountTrigger) else 0
         c.purging = int(trigger.purging)
         ev = evictor or Evictor()
@@ -250,7 +256,9 @@ class GpuListWindowOperator:
     def snapshot_key_group(self, kg):
         """(lists LIST_STATE_DTYPE, elements ELEM_DTYPE concatenated in list order) of key group kg.  Under
         ContinuousEventTimeTrigger the trigger_count column holds the windows' fire times (Long.MIN_VALUE: none)
-        and timer the registrations of both timers (1: maxTimestamp, 2: the fire time)."""
+        and timer the registrations of both timers (1: maxTimestamp, 2: the fire time).  Under DeltaTrigger
+        trigger_count holds the value bits of the window's last element and timer is 4 where that state is present
+        (0 otherwise; the trigger has no timer): a window purged or evicted empty is a row with n_elems 0."""
         L = N.lib()
         nl, ne = ctypes.c_int64(), ctypes.c_int64()
         self._check(L.fw_list_snapshot_key_group(self._h, int(kg), None, 0, 0, ctypes.byref(nl), ctypes.byref(ne)))
@@ -301,6 +309,9 @@ class GpuListWindowOperator:
         return {kg: self.snapshot_key_group(kg) for kg in self.key_group_range}
 
     def restore_key_group(self, kg, lists, elems):
+        """the columns of snapshot_key_group, appended to what the handle holds.  Refused with the handle unchanged:
+        timer bit 4 (DeltaTrigger's last element present) on a handle of another trigger, and any other timer bit on
+        a DeltaTrigger handle."""
         lists = np.ascontiguousarray(lists, dtype=LIST_STATE_DTYPE)
         elems = np.ascontiguousarray(elems, dtype=ELEM_DTYPE)
         lc = {f: np.ascontiguousarray(lists[f]) for f in LIST_STATE_DTYPE.names}

@@ -158,14 +158,14 @@ class EventTimeTrigger(Trigger):
 
 class PurgingTrigger(Trigger):
     """PurgingTrigger.of(EventTimeTrigger.create()) (PurgingTrigger.java:45-59); around
-    ContinuousEventTimeTrigger.of(interval) for both operators, around CountTrigger.of(n) for the window-contents
-    operator only."""
+    ContinuousEventTimeTrigger.of(interval) for both operators, around CountTrigger.of(n) or DeltaTrigger.of(threshold)
+    for the window-contents operator only."""
     purging = True
 
     def __init__(self, nested):
-        if not isinstance(nested, (EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger)):
-            raise ValueError("the GPU path offers PurgingTrigger only around EventTimeTrigger, CountTrigger or "
-                             "ContinuousEventTimeTrigger")
+        if not isinstance(nested, (EventTimeTrigger, CountTrigger, ContinuousEventTimeTrigger, DeltaTrigger)):
+            raise ValueError("the GPU path offers PurgingTrigger only around EventTimeTrigger, CountTrigger, "
+                             "ContinuousEventTimeTrigger or DeltaTrigger")
         self.nested = nested
 
     @staticmethod
@@ -220,6 +220,29 @@ class ContinuousEventTimeTrigger(Trigger):
 
     def __repr__(self):
         return f"ContinuousEventTimeTrigger({self.interval})"
+
+
+class DeltaTrigger(Trigger):
+    """DeltaTrigger.of(threshold, f, serializer) (DeltaTrigger.java:38-99) with the built-in DeltaFunction
+    f(old, new) = new.field - old.field over the operator's value field (the field's Java arithmetic, then widened to
+    double; TopSpeedWindowing's form, the mirror of DeltaEvictor's): a (key, window) keeps the last element that
+    fired (its first element to begin with) and FIREs at an element whose delta from it is > threshold.  It registers no
+    timer: a time window under it fires only while elements arrive.  For the window-contents operator
+    (GpuListWindowOperator) over tumbling, sliding and global windows; any other DeltaFunction is user code and stays
+    on the CPU."""
+
+    def __init__(self, threshold):
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("threshold must not be NaN")
+        self.threshold = threshold
+
+    @staticmethod
+    def of(threshold):
+        return DeltaTrigger(threshold)
+
+    def __repr__(self):
+        return f"DeltaTrigger({self.threshold})"
 
 
 class Evictor:

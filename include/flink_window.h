@@ -641,6 +641,22 @@ int fw_wire_encode_device(fw_wire* w, const fw_rows* rows, int64_t n, int32_t f6
  *              due timers run in ascending time, every firing a row of its own (an evictor runs per firing; a timer
  *              that finds no contents does not reach the trigger, so it is not re-armed: WindowOperator.java:446-459).
  *              More than 2^20 firings of one window in one advance are refused (FW_ERR_UNSUPPORTED, nothing changed);
+ *              FW_TRIGGER_DELTA (DeltaTrigger.of(trigger_threshold, f, serializer), DeltaTrigger.java:38-99, with the
+ *              built-in f(old, new) = new.field - old.field over the value field, in the field's Java arithmetic and
+ *              then widened to double: the mirror of the built-in DeltaEvictor function): per (key, window) the
+ *              ValueState "last-element".  onElement (:53-64): no state -> the element is stored, nothing fires;
+ *              f(last, element) > threshold (strict; a NaN delta never fires) -> the element is stored and the window
+ *              FIREs over the list up to it; else nothing.  onEventTime is CONTINUE and the trigger registers no timer:
+ *              a time window never fires at its maxTimestamp and has only the operator's cleanup timer; GlobalWindows
+ *              have none.  clear() drops the state at the window's cleanup (clearAllState); a purge (purging = 1)
+ *              or an evictor that empties the list leaves it.  Over tumbling, sliding (the state is per window) and
+ *              global windows.  Refused before the device is touched: FW_SESSION, with or without merging_state
+ *              (FW_ERR_ARG, "A merging window assigner cannot be used with a trigger that does not support merging.",
+ *              WindowedStream.trigger: DeltaTrigger does not override canMerge), a NaN threshold (FW_ERR_ARG), and a
+ *              join handle (FW_ERR_UNSUPPORTED: a DeltaFunction over the tagged union is user code).
+ *              fw_stats, as for CountTrigger's count: keyed_state_entries counts the windows with contents only (a
+ *              purged or emptied window keeps its last element, uncounted, until its cleanup), event_time_timers the
+ *              cleanup timers only;
  *   evictors   CountEvictor.of(n[, after]) (CountEvictor.java:50-78), TimeEvictor.of(ms[, after]) (TimeEvictor.java
  *              :54-104; a timestamp of Long.MIN_VALUE is "no timestamp": nothing is evicted when the first element
  *              has none), DeltaEvictor.of(threshold, f[, after]) with the built-in f(e, last) = last.field - e.field
@@ -655,6 +671,7 @@ int fw_wire_encode_device(fw_wire* w, const fw_rows* rows, int64_t n, int32_t f6
 #define FW_TRIGGER_EVENT_TIME 0
 #define FW_TRIGGER_COUNT 1
 #define FW_TRIGGER_CONTINUOUS_EVENT_TIME 2
+#define FW_TRIGGER_DELTA 3
 #define FW_EVICT_NONE 0
 #define FW_EVICT_COUNT 1
 #define FW_EVICT_TIME 2
@@ -683,7 +700,11 @@ typedef struct fw_list_config {
   double delta_threshold;    /* DeltaEvictor threshold                                            */
   int64_t expected_elements; /* sizing hint: elements held at once (0 = default)                  */
   int64_t max_batch;         /* largest n of one push (0 = 1 << 24)                               */
-  int64_t trigger_interval;  /* ContinuousEventTimeTrigger.of(interval), ms (> 0 for that trigger)      */
+  union {                    /* the last slot: the parameter of the trigger that has one of its own          */
+    int64_t trigger_interval;  /* ContinuousEventTimeTrigger.of(interval), ms (> 0 for that trigger)    */
+    double trigger_threshold;  /* FW_TRIGGER_DELTA: DeltaTrigger's threshold (not NaN), apart from the
+                                  DeltaEvictor's delta_threshold: a handle may use both                  */
+  };
 } fw_list_config;
 typedef struct fw_list_rows {
   int64_t *key, *start, *end, *count, *sum, *min, *max;
@@ -699,7 +720,12 @@ typedef struct fw_list_elems {
  * With FW_TRIGGER_CONTINUOUS_EVENT_TIME the trigger_count column carries the trigger's "fire-time" state instead
  * (the next early firing; Long.MIN_VALUE = null), and timer is a bit set: 1 = the maxTimestamp timer is registered,
  * 2 = the timer at the fire time is registered (it is not once a firing at maxTimestamp or a timer over empty
- * contents has consumed it). */
+ * contents has consumed it).
+ * With FW_TRIGGER_DELTA the trigger_count column carries the value bits of the trigger's "last-element" state (as the
+ * val column carries an element's) and timer bit 4 says that the state is present (0 otherwise: trigger_count is then
+ * 0); bits 1 and 2 are never set, the trigger has no timer.  A window whose list is empty (purged or evicted) but
+ * whose state is present is written with n_elems 0.  fw_list_restore_key_group refuses, with the handle unchanged, bit
+ * 4 on a handle of another trigger and any other bit on a FW_TRIGGER_DELTA handle (FW_ERR_ARG). */
 typedef struct fw_list_state {
   int64_t *key, *start, *end, *trigger_count, *timer, *n_elems;  /* per list   */
   int64_t *ts, *val, *ordinal;                                   /* elements   */

@@ -4,6 +4,9 @@ EvictingWindowOperator) on one MI355X, on the C2 stream shape: 1 s tumbling even
 keys, bounded out-of-orderness 200 ms, 1e8 records per event-second, a punctuated watermark after every batch of
 2^24 records.  The Iterable window function's input — every fired window's elements (timestamp, value, ordinal) in
 list order — is materialised in HBM and discarded (the sink); `--evictor count:N` / `time:MS` adds the evictor.
+`--trigger delta` (DeltaTrigger over the value field) and, beside it, `--trigger count:N` over the same tumbling windows
+run on a stream whose values are the records' arrival indices: a per-key increasing walk with steps of `--keys` on
+average, so the default threshold 7 x keys fires about every eighth element of a key, as CountTrigger.of(8) does.
 
 Algorithmic bytes per record (this build's figure; SURVEY §8d prices only the aggregating state): the input
 24 B, the element stored once (timestamp + value 16 B) and read once when its window fires (16 B), and emitted
@@ -33,7 +36,9 @@ def main():
     ap.add_argument("--evictor", default="none", help="none | count:N | time:MS")
     ap.add_argument("--trigger", default="event_time",
                     help="event_time | continuous: ContinuousEventTimeTrigger.of(--interval), early firings of every "
-                         "window | count:N: CountTrigger.of(N), with --sessions only (a merging_state handle)")
+                         "window | count:N: CountTrigger.of(N) (with --sessions: a merging_state handle) | delta: "
+                         "DeltaTrigger.of(--delta-threshold) over the value field")
+    ap.add_argument("--delta-threshold", type=float, default=0.0, help="DeltaTrigger's threshold (0: 7 x keys)")
     ap.add_argument("--sessions", type=int, default=0, metavar="GAP",
                     help="EventTimeSessionWindows.withGap(GAP ms) instead of the tumbling windows")
     ap.add_argument("--merging-state", action="store_true",
@@ -45,8 +50,8 @@ def main():
 
     import numpy as np
     import torch
-    from flink_amd import (ContinuousEventTimeTrigger, CountEvictor, CountTrigger, EventTimeSessionWindows, TimeEvictor,
-                           TumblingEventTimeWindows)
+    from flink_amd import (ContinuousEventTimeTrigger, CountEvictor, CountTrigger, DeltaTrigger, EventTimeSessionWindows,
+                           TimeEvictor, TumblingEventTimeWindows)
     from flink_amd.datagen import generate_device
     from flink_amd.listwindow import GpuListWindowOperator
 
@@ -56,14 +61,17 @@ def main():
     elif args.evictor.startswith("time:"):
         ev = TimeEvictor.of(int(args.evictor[5:]))
     per_window = args.rate * args.window // 1000
+    walk = not args.sessions and (args.trigger == "delta" or args.trigger.startswith("count:"))  # values = indices
     if args.trigger.startswith("count:"):
-        if not args.sessions:
-            ap.error("--trigger count:N is measured over --sessions")
-        trig, args.merging_state = CountTrigger.of(int(args.trigger[6:])), True
+        trig, args.merging_state = CountTrigger.of(int(args.trigger[6:])), bool(args.sessions)
+    elif args.trigger == "delta":
+        if args.sessions:
+            ap.error("--trigger delta: a merging assigner refuses the trigger")
+        trig = DeltaTrigger.of(args.delta_threshold or 7.0 * args.keys)
     elif args.trigger in ("event_time", "continuous"):
         trig = ContinuousEventTimeTrigger.of(args.interval) if args.trigger == "continuous" else None
     else:
-        ap.error("--trigger: event_time, continuous or count:N")
+        ap.error("--trigger: event_time, continuous, count:N or delta")
     if trig is not None:
         args.no_cpu_baseline = True  # (the ListState oracle has neither trigger: no CPU leg for them)
     assigner = EventTimeSessionWindows.with_gap(args.sessions) if args.sessions else TumblingEventTimeWindows.of(args.window)
@@ -75,6 +83,8 @@ def main():
     for s in range(args.warmup + args.steps):
         k, t, v, mx = generate_device(0x5EED, s * args.batch, args.batch, args.keys, ts_base=0, rate=args.rate,
                                       jitter=200, device=0)
+        if walk:
+            v = torch.arange(s * args.batch, (s + 1) * args.batch, dtype=torch.int64, device=dev)
         batches.append((k, t, v))
         m = max(m, int(mx.item()))
         wms.append(m - 200)
