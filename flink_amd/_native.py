@@ -198,6 +198,11 @@ SIGNATURES = {
                                                   ctypes.c_int64, I64P]),
     "fw_restore_key_group_fire": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwStateRows), VP,
                                                  ctypes.c_int64]),
+    "fw_create_count_trigger": (ctypes.c_int, [ctypes.POINTER(FwConfig), ctypes.c_int64, ctypes.POINTER(VP)]),
+    "fw_snapshot_key_group_trigger_count": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwStateRows), VP,
+                                                           ctypes.c_int64, I64P]),
+    "fw_restore_key_group_trigger_count": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwStateRows), VP,
+                                                          ctypes.c_int64]),
     "fw_key_groups_device": (ctypes.c_int, [VP, VP, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, VP, VP]),
     "fw_route_device": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_int32, VP, VP, VP, VP, VP, VP, ctypes.c_int64, VP]),

@@ -9028,6 +9028,470 @@ __global__ void k_cf_restore(DevCfg c, int32_t kg, StateCols in, const int64_t* 
   atomicMin((long long*)&tb.next_timer[p], (long long)fw_cf_next(M, C, df, dfl));
 }
 
+// ============================================================== CountTrigger over time windows (fw_create_count_trigger)
+// .trigger(CountTrigger.of(n)) on the aggregating operator, optionally inside PurgingTrigger (CountTrigger.java:47-85
+// under WindowOperator.processElement, WindowOperator.java:379-407).  Per element and window that is not late: add,
+// count += 1, and at count >= n clear the count and emit the accumulator as of that element.  The firing is inside the
+// push and depends on arrival order, so a push is a grouped, arrival-ordered segmented scan:
+//   an item = one (record, window that is not late), numbered in arrival order (record index, then the assigner's
+//   window order); every item finds or claims its window's slot; a stable sort by slot groups the items and keeps
+//   arrival order; rank r of an item in its group and the entry's count c0 give the firing ranks in closed form
+//   (r >= f0 = max(1, n - c0), (r - f0) % n == 0), so a row costs one scan element, whatever the window holds;
+//   the inclusive scan of {count, sum, min, max} is seeded with the entry's accumulator at the group's first item and
+//   restarts behind every firing rank under PurgingTrigger; the group's last item folds the scan and the new count
+//   into the entry.  The scan runs over chunks of FW_CT_CHUNK items (k_ct_scan<false>: the chunks' aggregates,
+//   k_ct_top: their exclusive scan, k_ct_scan<true>: the rows), so a group of any length carries across chunks.
+// Entries are read-only during the scan: the folded entries go to the regions' other buffer (free between two
+// watermarks) and k_ct_fold copies them back.
+__device__ __forceinline__ CtAcc ct_empty() { return CtAcc{0, 0, 0, 0, 0}; }
+// a fresh accumulator with one element (createAccumulator's +0.0 + v)
+__device__ __forceinline__ CtAcc ct_item(const DevCfg& c, int64_t v) {
+  CtAcc a;
+  a.cnt = 1;
+  a.flag = 0;
+  if (c.vtype == FW_VAL_F64) {
+    a.sum = __double_as_longlong(0.0 + __longlong_as_double(v));
+    a.mn = a.mx = f64_sortable(v);
+  } else {
+    a.sum = v;
+    a.mn = a.mx = v;
+  }
+  return a;
+}
+// the segmented scan's operator (a before b): b alone when a segment starts in b
+__device__ __forceinline__ CtAcc ct_comb(const DevCfg& c, const CtAcc& a, const CtAcc& b) {
+  if (b.cnt == 0 && !b.flag) return a;
+  CtAcc r = b;
+  r.flag = a.flag | b.flag;
+  if (b.flag || a.cnt == 0) return r;
+  r.cnt = a.cnt + b.cnt;
+  r.sum = c.vtype == FW_VAL_F64 ? __double_as_longlong(__longlong_as_double(a.sum) + __longlong_as_double(b.sum))
+                                : jadd(a.sum, b.sum);
+  r.mn = b.mn < a.mn ? b.mn : a.mn;
+  r.mx = b.mx > a.mx ? b.mx : a.mx;
+  return r;
+}
+__device__ __forceinline__ CtAcc ct_shfl_up(const CtAcc& x, int o) {
+  CtAcc y;
+  y.cnt = __shfl_up((long long)x.cnt, o, 64);
+  y.sum = __shfl_up((long long)x.sum, o, 64);
+  y.mn = __shfl_up((long long)x.mn, o, 64);
+  y.mx = __shfl_up((long long)x.mx, o, 64);
+  y.flag = __shfl_up((int)x.flag, o, 64);
+  return y;
+}
+// inclusive scan over the workgroup's NT threads (sw: NT / 64 elements of LDS); *excl = the same without the
+// thread's own element, *total = all of them
+template <int NT>
+__device__ __forceinline__ CtAcc ct_block_scan(const DevCfg& c, CtAcc x, CtAcc* sw, CtAcc* excl, CtAcc* total) {
+  const int lane = __lane_id(), wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const CtAcc y = ct_shfl_up(x, o);
+    if (lane >= o) x = ct_comb(c, y, x);
+  }
+  CtAcc ex = ct_shfl_up(x, 1);
+  if (lane == 0) ex = ct_empty();
+  if (lane == 63) sw[wid] = x;
+  __syncthreads();
+  CtAcc pre = ct_empty(), tot = ct_empty();
+  for (int w = 0; w < NT / 64; w++) {
+    if (w == wid) pre = tot;
+    tot = ct_comb(c, tot, sw[w]);
+  }
+  *total = tot;
+  *excl = ct_comb(c, pre, ex);
+  __syncthreads();
+  return ct_comb(c, pre, x);
+}
+
+// the record's class and windows as the push takes them: *nw windows from *last down, of which those with
+// cleanupTime > wm are not late (isWindowLate, WindowOperator.java:591-593); false = the record is left out
+// (outside the KeyGroupRange, no timestamp, a refused end of the long range)
+__device__ __forceinline__ bool ct_windows(const DevCfg& c, int64_t wm, int64_t k, int64_t t, const int32_t* kh,
+                                           int64_t i, int32_t* p, int64_t* last, int* nw, int* why) {
+  *p = partition_of(c, k, key_hash_of(c.key_kind, k, kh, i));
+  *why = 0;
+  if (*p < 0) {
+    *why = 1;
+    return false;
+  }
+  const int cls = classify(c, wm, t, last, nw, k, 0);
+  if (cls == CLS_BADTS) *why = 2;
+  if (cls == CLS_RANGE) *why = 3;
+  return *why == 0;
+}
+__device__ __forceinline__ bool ct_window_live(const DevCfg& c, int64_t wm, int64_t last, int wi, int64_t* s, int64_t* e) {
+  *s = jsub(last, (int64_t)wi * c.slide);
+  *e = jadd(*s, c.size);
+  return cleanup_of(*e, c.lateness) > wm;
+}
+
+// items per record; key-group, timestamp and range errors; late records (an element all of whose windows were late
+// and that is late itself: side output or numLateRecordsDropped, WindowOperator.java:409-419)
+__global__ __launch_bounds__(256) void k_ct_count(DevCfg c, int64_t wm, const int64_t* __restrict__ key,
+                                                  const int64_t* __restrict__ ts, const int64_t* __restrict__ val,
+                                                  const int32_t* __restrict__ kh, int64_t n,
+                                                  uint32_t* __restrict__ nitem, DevSide side, Status* st) {
+  int bad_kg = 0, bad_ts = 0, bad_range = 0;
+  unsigned long long late = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = key[i], t = ts[i];
+    int32_t p;
+    int64_t last = 0;
+    int nw = 0, why;
+    uint32_t live = 0;
+    if (ct_windows(c, wm, k, t, kh, i, &p, &last, &nw, &why)) {
+      for (int wi = 0; wi < nw; wi++) {  // (nw <= DevCfg::wpr)
+        int64_t s, e;
+        live += ct_window_live(c, wm, last, wi, &s, &e);
+      }
+      if (!live && jadd(t, c.lateness) <= wm) {
+        if (c.side_output)
+          side_one(side, st, k, t, val[i]);
+        else
+          late++;
+      }
+    } else {
+      bad_kg += why == 1;
+      bad_ts += why == 2;
+      bad_range += why == 3;
+    }
+    nitem[i] = live;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) nitem[n] = 0;  // (the scan leaves the total here)
+  if (late) atomicAdd(&st->late_dropped, late);
+  if (bad_kg) atomicAdd(&st->kg_errors, bad_kg);
+  if (bad_ts) atomicAdd(&st->ts_errors, bad_ts);
+  if (bad_range) atomicAdd(&st->range_errors, bad_range);
+}
+
+constexpr uint32_t CT_NONE = 0xffffffffu;
+// Find the live slot of window (k, [s, e)) of partition p, or claim one: >= 0 the global slot, -1 the region is at its
+// load limit (the host grows the table), -2 a slot with this window's fingerprint is being claimed in this launch
+// (the next round finds it published).  A claimed slot stays SLOT_BUSY | fingerprint until k_ct_publish, behind the
+// launch boundary that makes its entry visible; nobody waits inside a launch.  SERIAL: the single thread of the last
+// round publishes at once.
+template <bool SERIAL>
+__device__ __forceinline__ int64_t ct_find_or_claim(const DevCfg& c, const DevTable& tb, int32_t p, int64_t k, int64_t s,
+                                                    int64_t e) {
+  const Region r = region_of(c, tb, p, tb.cur[p]);
+  const uint64_t h = slot_hash(c, k, s);
+  const uint32_t want = live_word(h), busy = SLOT_BUSY | tag_of(h);
+  for (uint32_t i = 0; i <= r.mask; i++) {
+    const uint32_t sl = ((uint32_t)h + i) & r.mask;
+    uint32_t w = ld_state(r.state + sl);
+    if (w == SLOT_EMPTY) {
+      // (the live count is taken by the claim's winner only: the lanes that race for one new window's slot must not
+      // count against the limit, or a push that opens many windows at once would look like a full region)
+      if (__hip_atomic_load(&tb.live[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= region_limit(c.log_r)) return -1;
+      w = atomicCAS(r.state + sl, (uint32_t)SLOT_EMPTY, busy);
+      if (w == SLOT_EMPTY) {
+        atomicAdd(&tb.live[p], 1);
+        Entry ne;
+        ne.key = k;
+        ne.start = s;
+        ne.end = e;
+        acc_clear(c, ne);
+        ne.meta = 0;
+        r.ent[sl] = ne;
+        if constexpr (SERIAL) {
+          __threadfence();
+          __hip_atomic_store(r.state + sl, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        atomicMin((long long*)&tb.next_timer[p], (long long)cleanup_of(e, c.lateness));  // registerCleanupTimer
+        return ((int64_t)p << c.log_r) | sl;
+      }
+      // (another window took the slot: w is its word)
+    }
+    if (w == want) {
+      const Entry& x = r.ent[sl];
+      if (x.key == k && x.start == s && x.end == e) return ((int64_t)p << c.log_r) | sl;
+    } else if (w == busy) {
+      return -2;
+    }
+  }
+  return -1;
+}
+// the items of record i that have no slot yet; 1 = some region was at its limit, 2 = some item waits for a round
+template <bool SERIAL>
+__device__ __forceinline__ int ct_insert_record(const DevCfg& c, int64_t wm, const int64_t* __restrict__ key,
+                                                const int64_t* __restrict__ ts, const int32_t* __restrict__ kh,
+                                                int64_t i, const uint32_t* __restrict__ off, uint32_t* __restrict__ sk,
+                                                uint32_t* __restrict__ sv, const DevTable& tb) {
+  const uint32_t j0 = off[i], j1 = off[i + 1];
+  if (j0 == j1) return 0;
+  const int64_t k = key[i], t = ts[i];
+  int32_t p;
+  int64_t last = 0;
+  int nw = 0, why, res = 0;
+  if (!ct_windows(c, wm, k, t, kh, i, &p, &last, &nw, &why)) return 0;  // (cannot happen: it has items)
+  uint32_t j = j0;
+  for (int wi = 0; wi < nw && j < j1; wi++) {
+    int64_t s, e;
+    if (!ct_window_live(c, wm, last, wi, &s, &e)) continue;
+    if (sk[j] == CT_NONE) {
+      const int64_t g = ct_find_or_claim<SERIAL>(c, tb, p, k, s, e);
+      if (g >= 0) {
+        sk[j] = (uint32_t)g;
+        sv[j] = (uint32_t)i;
+      } else {
+        res |= g == -1 ? 1 : 2;
+      }
+    }
+    j++;
+  }
+  return res;
+}
+template <int ROUND>
+__global__ __launch_bounds__(256) void k_ct_insert(DevCfg c, int64_t wm, const int64_t* __restrict__ key,
+                                                   const int64_t* __restrict__ ts, const int32_t* __restrict__ kh,
+                                                   int64_t n, const uint32_t* __restrict__ off,
+                                                   uint32_t* __restrict__ sk, uint32_t* __restrict__ sv, DevTable tb,
+                                                   unsigned long long* ctr, uint32_t* __restrict__ retry) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int res = ct_insert_record<false>(c, wm, key, ts, kh, i, off, sk, sv, tb);
+    if (res & 1) atomicAdd(&ctr[1], 1ull);
+    if constexpr (ROUND == 1) {
+      if (res & 2) retry[atomicAdd(&ctr[2], 1ull)] = (uint32_t)i;
+    }
+  }
+}
+// what two rounds left (three windows of one fingerprint on one probe chain claimed in one push): one thread, in turn
+__global__ void k_ct_insert_rest(DevCfg c, int64_t wm, const int64_t* __restrict__ key, const int64_t* __restrict__ ts,
+                                 const int32_t* __restrict__ kh, const uint32_t* __restrict__ off,
+                                 uint32_t* __restrict__ sk, uint32_t* __restrict__ sv, DevTable tb,
+                                 unsigned long long* ctr, const uint32_t* __restrict__ retry) {
+  const unsigned long long m = ctr[2];
+  for (unsigned long long q = 0; q < m; q++)  // (m: records of the push, counted by round 1)
+    if (ct_insert_record<true>(c, wm, key, ts, kh, (int64_t)retry[q], off, sk, sv, tb) & 1) ctr[1] += 1;
+}
+// the slots claimed by the launch before become live
+__global__ __launch_bounds__(256) void k_ct_publish(DevCfg c, const uint32_t* __restrict__ sk, int64_t m, DevTable tb) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t g = sk[j];
+    if (g == CT_NONE) continue;
+    const int32_t p = (int32_t)(g >> c.log_r);
+    uint32_t* w = tb.state[tb.cur[p]] + g;
+    if (st_kind(ld_state(w)) != SLOT_BUSY) continue;
+    const Entry& e = tb.ent[tb.cur[p]][g];
+    __hip_atomic_store(w, live_word(slot_hash(c, e.key, e.start)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// sk sorted: where each slot's group starts
+__global__ __launch_bounds__(256) void k_ct_bounds(const uint32_t* __restrict__ sk, int64_t m, uint32_t* __restrict__ first) {
+  for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < m; x += (int64_t)gridDim.x * blockDim.x)
+    if (x == 0 || sk[x - 1] != sk[x]) first[sk[x]] = (uint32_t)x;
+}
+// does the trigger fire at the group's rank r (1-based), the count before the push being c0?
+__device__ __forceinline__ bool ct_fires(int64_t nf, int64_t c0, uint32_t r) {
+  const uint32_t f0 = c0 >= nf ? 1u : (uint32_t)(nf - c0);  // (nf < 2^31; the comparison is >=: a count of n or more
+  return r >= f0 && (r - f0) % (uint32_t)nf == 0;            // fires at the next element)
+}
+// the count after a group of m items
+__device__ __forceinline__ int64_t ct_count_after(int64_t nf, int64_t c0, uint32_t m) {
+  const uint32_t f0 = c0 >= nf ? 1u : (uint32_t)(nf - c0);
+  if (m < f0) return c0 + m;
+  return (int64_t)((m - f0) % (uint32_t)nf);
+}
+// the rows the push fires, exactly: per group of m items with count c0, the firing ranks f0, f0 + n, ... <= m
+// (ctr[3], zeroed by the insert): the host sizes the row buffer for them before anything is emitted
+__global__ __launch_bounds__(256) void k_ct_rows(DevCfg c, int64_t nf, const uint32_t* __restrict__ sk,
+                                                 const uint32_t* __restrict__ first, int64_t m, DevTable tb,
+                                                 unsigned long long* ctr) {
+  unsigned long long rows = 0;
+  for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < m; x += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t g = sk[x];
+    if (x + 1 != m && sk[x + 1] == g) continue;
+    const uint32_t r = (uint32_t)(x - first[g]) + 1u;
+    const int64_t c0 = tb.ent[tb.cur[g >> c.log_r]][g].meta >> FW_CT_SHIFT;
+    const uint32_t f0 = c0 >= nf ? 1u : (uint32_t)(nf - c0);
+    if (r >= f0) rows += (r - f0) / (uint32_t)nf + 1u;
+  }
+  if (rows) atomicAdd(&ctr[3], rows);
+}
+// EMIT false: tile[chunk] = the chunk's aggregate.  EMIT true: tile[chunk] = what the chunks before carry into it; the
+// rows (counted per step of the chunk, then written: the host made room for k_ct_rows' count) and the folded entries
+template <bool EMIT>
+__global__ __launch_bounds__(FW_CT_THREADS) void k_ct_scan(DevCfg c, int64_t nf, const uint32_t* __restrict__ sk,
+                                                           const uint32_t* __restrict__ sv,
+                                                           const int64_t* __restrict__ val,
+                                                           const uint32_t* __restrict__ first, int64_t m, DevTable tb,
+                                                           CtAcc* __restrict__ tile, DevRows out, Status* st) {
+  __shared__ CtAcc sw[FW_CT_THREADS / 64];
+  __shared__ uint32_t sws[FW_CT_THREADS / 64 + 1];
+  __shared__ unsigned long long base_s;
+  CtAcc run = EMIT ? tile[blockIdx.x] : ct_empty();
+  const int64_t x0 = (int64_t)blockIdx.x * FW_CT_CHUNK;
+  unsigned long long fired = 0;
+  for (int it = 0; it < FW_CT_ITERS; it++) {
+    const int64_t xb = x0 + (int64_t)it * FW_CT_THREADS;
+    if (xb >= m) break;  // (uniform)
+    const int64_t x = xb + threadIdx.x;
+    CtAcc a = ct_empty();
+    bool fire = false, lastg = false;
+    uint32_t g = 0, r = 0;
+    int64_t c0 = 0;
+    int cur = 0;
+    if (x < m) {
+      g = sk[x];
+      const uint32_t f = first[g];
+      r = (uint32_t)(x - f) + 1u;
+      cur = tb.cur[g >> c.log_r];
+      const Entry& en = tb.ent[cur][g];
+      c0 = en.meta >> FW_CT_SHIFT;
+      fire = ct_fires(nf, c0, r);
+      a = ct_item(c, val[sv[x]]);
+      if (r == 1 && en.cnt > 0) a = ct_comb(c, CtAcc{en.cnt, en.sum, en.mn, en.mx, 0}, a);
+      a.flag = r == 1 || (c.purging && ct_fires(nf, c0, r - 1));
+      lastg = x + 1 == m || sk[x + 1] != g;
+    }
+    CtAcc ex, tot;
+    CtAcc inc = ct_block_scan<FW_CT_THREADS>(c, a, sw, &ex, &tot);
+    inc = ct_comb(c, run, inc);
+    run = ct_comb(c, run, tot);
+    if constexpr (EMIT) {
+      uint32_t total;
+      const uint32_t pos0 = block_excl_scan(fire ? 1u : 0u, sws, &total);
+      if (threadIdx.x == 0) base_s = total ? atomicAdd(&st->out_rows, (unsigned long long)total) : 0ull;
+      __syncthreads();
+      if (fire || lastg) {
+        Entry e = tb.ent[cur][g];
+        e.cnt = inc.cnt;
+        e.sum = inc.sum;
+        e.mn = inc.mn;
+        e.mx = inc.mx;
+        if (fire) {
+          const unsigned long long pos = base_s + pos0;
+          if ((int64_t)pos < out.cap)
+            write_row(c, out, pos, e);
+          else
+            atomicOr(&st->flags, FW_STATUS_OUT_FULL);  // cannot happen: the host made room for the counted rows
+        }
+        if (lastg) {
+          if (fire && c.purging) acc_clear(c, e);  // FIRE_AND_PURGE: the window stays, emptied, with its cleanup timer
+          e.meta = ct_count_after(nf, c0, r) << FW_CT_SHIFT;
+          tb.ent[cur ^ 1][g] = e;
+        }
+      }
+      fired += total;
+    }
+  }
+  if constexpr (EMIT) {
+    if (threadIdx.x == 0 && fired) atomicAdd(&st->fired_total, fired);
+  } else {
+    if (threadIdx.x == 0) tile[blockIdx.x] = run;
+  }
+}
+// the chunks' aggregates -> what each chunk is carried (in place)
+__global__ __launch_bounds__(1024) void k_ct_top(DevCfg c, CtAcc* __restrict__ tile, int64_t nt) {
+  __shared__ CtAcc sw[1024 / 64];
+  CtAcc carry = ct_empty();
+  for (int64_t b0 = 0; b0 < nt; b0 += 1024) {
+    const int64_t i = b0 + threadIdx.x;
+    const CtAcc a = i < nt ? tile[i] : ct_empty();
+    CtAcc ex, tot;
+    ct_block_scan<1024>(c, a, sw, &ex, &tot);
+    if (i < nt) tile[i] = ct_comb(c, carry, ex);
+    carry = ct_comb(c, carry, tot);
+  }
+}
+// the folded entries back from the regions' other buffer
+__global__ __launch_bounds__(256) void k_ct_fold(DevCfg c, const uint32_t* __restrict__ sk, int64_t m, DevTable tb) {
+  for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < m; x += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t g = sk[x];
+    if (x + 1 != m && sk[x + 1] == g) continue;
+    const int cur = tb.cur[g >> c.log_r];
+    tb.ent[cur][g] = tb.ent[cur ^ 1][g];
+  }
+}
+// numKeyedStateEntries: the windows with contents; numEventTimeTimers: one cleanup timer per window in flight, the
+// emptied ones included (a cleanup time of Long.MAX_VALUE registers none, WindowOperator.java:611-617)
+__global__ __launch_bounds__(FW_FIRE_THREADS) void k_ct_stats(DevCfg c, DevTable tb, unsigned long long* out3) {
+  const int32_t p = blockIdx.x;
+  const Region r = region_of(c, tb, p, tb.cur[p]);
+  unsigned long long live = 0, timers = 0;
+  for (uint32_t s = threadIdx.x; s <= r.mask; s += blockDim.x) {
+    if (st_kind(ld_state(r.state + s)) != SLOT_LIVE) continue;
+    const Entry& e = r.ent[s];
+    live += e.cnt > 0;
+    timers += cleanup_of(e.end, c.lateness) != LMAX;
+  }
+  if (live) atomicAdd(&out3[0], live);
+  if (timers) atomicAdd(&out3[1], timers);
+}
+// keyed-state snapshot with the trigger's count (k_snapshot's rows; an emptied window is a row too: its count and its
+// cleanup timer are state)
+__global__ __launch_bounds__(FW_FIRE_THREADS) void k_ct_snapshot(DevCfg c, DevTable tb, int32_t p0, StateCols out,
+                                                                int64_t* __restrict__ tcount, unsigned long long* count) {
+  __shared__ uint32_t sw[FW_FIRE_THREADS / 64 + 1];
+  __shared__ unsigned long long base_s;
+  const int32_t p = p0 + blockIdx.x;
+  const Region r = region_of(c, tb, p, tb.cur[p]);
+  const uint32_t R = r.mask + 1;
+  for (uint32_t s0 = 0; s0 < R; s0 += blockDim.x) {
+    const uint32_t s = s0 + threadIdx.x;
+    const bool live = s < R && st_kind(ld_state(r.state + s)) == SLOT_LIVE;
+    uint32_t total;
+    const uint32_t pos = block_excl_scan(live ? 1u : 0u, sw, &total);
+    if (threadIdx.x == 0) base_s = total ? atomicAdd(count, (unsigned long long)total) : 0ull;
+    __syncthreads();
+    if (live) {
+      const Entry e = r.ent[s];
+      const unsigned long long o = base_s + pos;
+      out.key[o] = e.key;
+      out.start[o] = e.start;
+      out.end[o] = e.end;
+      out.cnt[o] = e.cnt;
+      out.sum[o] = sum_out(c, e.sum);
+      out.mn[o] = mn_out(c, e.mn);
+      out.mx[o] = mx_out(c, e.mx);
+      out.timer[o] = 0;  // (no timer at maxTimestamp: CountTrigger.onEventTime is never asked)
+      tcount[o] = e.meta >> FW_CT_SHIFT;
+    }
+    __syncthreads();
+  }
+}
+// restore of such rows; a row whose (key, window) is present merges, the counts add without firing
+// (CountTrigger.onMerge / the count's ReducingState, Sum)
+__global__ void k_ct_restore(DevCfg c, int32_t kg, StateCols in, const int64_t* __restrict__ tcount, int64_t n,
+                             DevTable tb, Status* st, const int32_t* round_of, int32_t round) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || (round_of && round_of[i] != round)) return;
+  const int32_t p = restore_partition(c, kg, in.key[i]);
+  if (p < 0) return;
+  Entry d;
+  d.key = in.key[i];
+  d.start = in.start[i];
+  d.end = in.end[i];
+  d.cnt = in.cnt[i];
+  d.sum = in.sum[i];
+  d.mn = c.vtype == FW_VAL_F64 ? f64_sortable(in.mn[i]) : in.mn[i];
+  d.mx = c.vtype == FW_VAL_F64 ? f64_sortable(in.mx[i]) : in.mx[i];
+  if (d.cnt == 0) acc_clear(c, d);
+  d.meta = tcount[i] << FW_CT_SHIFT;
+  const Region r = region_of(c, tb, p, tb.cur[p]);
+  const uint64_t h = slot_hash(c, d.key, d.start);
+  const int32_t found = region_find(r, h, d.key, d.start, d.end);
+  if (found >= 0) {
+    Entry cur = r.ent[found];
+    acc_merge(c, cur, d);
+    cur.meta += d.meta;
+    r.ent[found] = cur;
+    return;
+  }
+  const int32_t s = region_claim(r, h, SLOT_BUSY);
+  if (s < 0) {
+    atomicOr(&st->flags, FW_STATUS_STATE_LOST);
+    return;
+  }
+  r.ent[s] = d;
+  __threadfence();
+  __hip_atomic_store(r.state + s, live_word(h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  atomicAdd(&tb.live[p], 1);
+  atomicMin((long long*)&tb.next_timer[p], (long long)cleanup_of(d.end, c.lateness));
+}
+
 }  // namespace
 
 // ============================================================================== launchers
@@ -9332,6 +9796,70 @@ void launch_cont_restore(const DevCfg& c, int32_t kg, StateCols in, const int64_
   const dim3 grid((unsigned)((n + 255) / 256));
   for (int32_t r = 0; r < rounds; r++)
     hipLaunchKernelGGL(k_cf_restore, grid, dim3(256), 0, s, c, kg, in, fire, n, tb, st, round_of, r);
+}
+
+// ---- CountTrigger over time windows
+size_t ct_sort_bytes(int64_t n) {
+  size_t a = 0;
+  rocprim::double_buffer<uint32_t> ks(nullptr, nullptr), vs(nullptr, nullptr);
+  (void)rocprim::radix_sort_pairs(nullptr, a, ks, vs, (size_t)n, 0, 32);
+  return a;
+}
+static inline unsigned ct_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192)); }
+void launch_ct_count(const DevCfg& c, int64_t wm, const int64_t* key, const int64_t* ts, const int64_t* val,
+                     const int32_t* kh, int64_t n, const CtBuf& b, DevSide side, Status* st, hipStream_t s) {
+  hipLaunchKernelGGL(k_ct_count, dim3(ct_grid(n)), dim3(256), 0, s, c, wm, key, ts, val, kh, n, b.nitem, side, st);
+  launch_scan(b.nitem, n + 1, b.scan_tmp, s, nullptr);
+}
+void launch_ct_insert(const DevCfg& c, int64_t wm, const int64_t* key, const int64_t* ts, const int32_t* kh, int64_t n,
+                      int64_t items, const CtBuf& b, DevTable tb, hipStream_t s) {
+  (void)hipMemsetAsync(b.sk[0], 0xff, (size_t)items * sizeof(uint32_t), s);
+  (void)hipMemsetAsync(b.ctr, 0, 4 * sizeof(unsigned long long), s);
+  hipLaunchKernelGGL(k_ct_insert<0>, dim3(ct_grid(n)), dim3(256), 0, s, c, wm, key, ts, kh, n,
+                     (const uint32_t*)b.nitem, b.sk[0], b.sv[0], tb, b.ctr, b.retry);
+  hipLaunchKernelGGL(k_ct_publish, dim3(ct_grid(items)), dim3(256), 0, s, c, (const uint32_t*)b.sk[0], items, tb);
+  hipLaunchKernelGGL(k_ct_insert<1>, dim3(ct_grid(n)), dim3(256), 0, s, c, wm, key, ts, kh, n,
+                     (const uint32_t*)b.nitem, b.sk[0], b.sv[0], tb, b.ctr, b.retry);
+  hipLaunchKernelGGL(k_ct_publish, dim3(ct_grid(items)), dim3(256), 0, s, c, (const uint32_t*)b.sk[0], items, tb);
+  hipLaunchKernelGGL(k_ct_insert_rest, dim3(1), dim3(1), 0, s, c, wm, key, ts, kh, (const uint32_t*)b.nitem, b.sk[0],
+                     b.sv[0], tb, b.ctr, (const uint32_t*)b.retry);
+}
+int launch_ct_group(const DevCfg& c, int64_t items, const CtBuf& b, DevTable tb, hipStream_t s) {
+  unsigned bits = 1;
+  while (((int64_t)1 << bits) < ((int64_t)c.P << c.log_r)) bits++;
+  rocprim::double_buffer<uint32_t> ks(b.sk[0], b.sk[1]), vs(b.sv[0], b.sv[1]);
+  size_t bytes = b.tmp_bytes;
+  (void)rocprim::radix_sort_pairs(b.tmp, bytes, ks, vs, (size_t)items, 0, bits, s);  // stable: arrival order per window
+  const uint32_t* sk = ks.current();
+  hipLaunchKernelGGL(k_ct_bounds, dim3(ct_grid(items)), dim3(256), 0, s, sk, items, b.first);
+  hipLaunchKernelGGL(k_ct_rows, dim3(ct_grid(items)), dim3(256), 0, s, c, b.nfire, sk, (const uint32_t*)b.first, items,
+                     tb, b.ctr);
+  return sk == b.sk[1] ? 1 : 0;  // (keys and values change halves together)
+}
+void launch_ct_fire(const DevCfg& c, const int64_t* val, int64_t items, const CtBuf& b, int half, DevTable tb,
+                    DevRows out, Status* st, hipStream_t s) {
+  const uint32_t* sk = b.sk[half];
+  const uint32_t* sv = b.sv[half];
+  const int64_t nt = (items + FW_CT_CHUNK - 1) / FW_CT_CHUNK;
+  hipLaunchKernelGGL(k_ct_scan<false>, dim3((unsigned)nt), dim3(FW_CT_THREADS), 0, s, c, b.nfire, sk, sv, val,
+                     (const uint32_t*)b.first, items, tb, b.tile, out, st);
+  hipLaunchKernelGGL(k_ct_top, dim3(1), dim3(1024), 0, s, c, b.tile, nt);
+  FW_LAUNCH_MAIN(k_ct_scan<true>, dim3((unsigned)nt), dim3(FW_CT_THREADS), 0, s, c, b.nfire, sk, sv, val,
+                 (const uint32_t*)b.first, items, tb, b.tile, out, st);
+  hipLaunchKernelGGL(k_ct_fold, dim3(ct_grid(items)), dim3(256), 0, s, c, sk, items, tb);
+}
+void launch_ct_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t s) {
+  hipLaunchKernelGGL(k_ct_stats, dim3(c.P), dim3(FW_FIRE_THREADS), 0, s, c, tb, out3);
+}
+void launch_ct_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, StateCols out, int64_t* tcount,
+                        unsigned long long* count, hipStream_t s) {
+  hipLaunchKernelGGL(k_ct_snapshot, dim3(np), dim3(FW_FIRE_THREADS), 0, s, c, tb, p0, out, tcount, count);
+}
+void launch_ct_restore(const DevCfg& c, int32_t kg, StateCols in, const int64_t* tcount, int64_t n, DevTable tb,
+                       Status* st, const int32_t* round_of, int32_t rounds, hipStream_t s) {
+  const dim3 grid((unsigned)((n + 255) / 256));
+  for (int32_t r = 0; r < rounds; r++)
+    hipLaunchKernelGGL(k_ct_restore, grid, dim3(256), 0, s, c, kg, in, tcount, n, tb, st, round_of, r);
 }
 
 void launch_fire(const DevCfg& c0, int64_t wm, DevTable tb, DevRows out, Status* st, hipStream_t s) {

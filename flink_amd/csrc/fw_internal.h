@@ -478,6 +478,30 @@ struct PartialRec {
 
 // ---------------------------------------------------------------- launchers (fw_device.hip)
 typedef hipStream_t hipStream_t_;
+// CountTrigger over time windows (fw_create_count_trigger; the launchers below): the scan's element and a handle's
+// buffers for one push
+enum { FW_CT_SHIFT = 3 };
+struct CtAcc {  // an accumulator and "a segment starts in here"
+  int64_t cnt, sum, mn, mx;
+  int64_t flag;
+};
+constexpr int FW_CT_THREADS = 256, FW_CT_ITERS = 16, FW_CT_CHUNK = FW_CT_THREADS * FW_CT_ITERS;
+struct CtBuf {
+  int64_t nfire = 0;            // CountTrigger.of(nfire); 0 = not such a handle
+  int64_t mi = 0;               // items of the largest push: max_batch * wpr
+  uint32_t* nitem = nullptr;    // [max_batch + 1] items per record, scanned in place
+  uint32_t* scan_tmp = nullptr;
+  uint32_t* sk[2] = {nullptr, nullptr};  // [mi] the items' global slots (sort keys)
+  uint32_t* sv[2] = {nullptr, nullptr};  // [mi] the items' records (sort values)
+  uint32_t* first = nullptr;    // [table slots] sorted position of the slot's first item of this push
+  uint32_t* retry = nullptr;    // [max_batch] records the second insert round left to the serial one
+  unsigned long long* ctr = nullptr;  // [4]: 1 = items that found their region at its limit, 2 = retry list length,
+                                      //      3 = the rows the push fires
+  CtAcc* tile = nullptr;        // [mi / FW_CT_CHUNK + 2]
+  void* tmp = nullptr;          // the sort's
+  size_t tmp_bytes = 0;
+};
+
 namespace fwdev {
 // fw_profile's dispatch timing (set by the runtime around one launch helper): when `a` is set, the helper issues
 // its kind's main kernel with hipExtLaunchKernelGGL and these start / stop events, which take that dispatch's own
@@ -541,6 +565,30 @@ void launch_cont_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, 
                           unsigned long long* count, hipStream_t_ s);
 void launch_cont_restore(const DevCfg& c, int32_t kg, StateCols in, const int64_t* fire, int64_t n, DevTable tb,
                          Status* st, const int32_t* round_of, int32_t rounds, hipStream_t_ s);
+// ---- CountTrigger over time windows (fw_create_count_trigger; fw_device.hip "CountTrigger over time windows").  The
+// trigger's count rides in Entry::meta above FW_CT_SHIFT (bit 0, FW_TIMER, stays clear: this trigger registers no timer
+// at maxTimestamp, so k_fire only drops such an entry at its cleanup time).  A push is one item per (record, window
+// that is not late), in arrival order:
+//   count (items per record; errors, late records) -> scan -> insert (find or claim each item's slot; two rounds and
+//   a serial rest, a region at its load limit asks the host to grow) -> stable sort by slot -> bounds -> the rows
+//   the push fires, counted -> host: row buffer -> segmented scan (chunk aggregates, their scan, rows) -> fold.
+size_t ct_sort_bytes(int64_t n);
+void launch_ct_count(const DevCfg& c, int64_t wm, const int64_t* key, const int64_t* ts, const int64_t* val,
+                     const int32_t* kh, int64_t n, const CtBuf& b, DevSide side, Status* st, hipStream_t_ s);
+// every item's slot into b.sk[0] / record into b.sv[0]; ctr[1] != 0 afterwards: grow the table and call it again
+void launch_ct_insert(const DevCfg& c, int64_t wm, const int64_t* key, const int64_t* ts, const int32_t* kh, int64_t n,
+                      int64_t items, const CtBuf& b, DevTable tb, hipStream_t_ s);
+// stable sort by slot, the groups' bounds, ctr[3] = the rows the push fires; returns the half of b.sk / b.sv that
+// holds the sorted items
+int launch_ct_group(const DevCfg& c, int64_t items, const CtBuf& b, DevTable tb, hipStream_t_ s);
+// scan, rows, fold (the row buffer holds ctr[3] more rows)
+void launch_ct_fire(const DevCfg& c, const int64_t* val, int64_t items, const CtBuf& b, int half, DevTable tb,
+                    DevRows out, Status* st, hipStream_t_ s);
+void launch_ct_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t_ s);
+void launch_ct_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, StateCols out, int64_t* tcount,
+                        unsigned long long* count, hipStream_t_ s);
+void launch_ct_restore(const DevCfg& c, int32_t kg, StateCols in, const int64_t* tcount, int64_t n, DevTable tb,
+                       Status* st, const int32_t* round_of, int32_t rounds, hipStream_t_ s);
 int64_t pane_nt_floor(const DevCfg& c, int64_t wm);  // host: DevCfg::nt_floor of a launch at watermark wm
 // FW_AGG_HLL: fold the batch's records into the registers of their (key, window) entries (after aggregate)
 void launch_hll_update(const DevCfg& c, const PRec* part, const uint32_t* offs, int32_t T, int64_t n, DevTable tb,

@@ -135,6 +135,9 @@ struct fw_op {
   // the table when it grows) and the counting pass's two counters.  Allocated for such handles only.
   uint32_t* cf_first = nullptr;
   unsigned long long* cf_ctr = nullptr;
+  // CountTrigger over time windows (fw_create_count_trigger): ct.nfire != 0, the push's item buffers.  Allocated for
+  // such handles only.
+  CtBuf ct;
   uint32_t range_seen = 0;     // Status::range_errors as last settled (the device only adds to it)
   int64_t range_pending = 0;   // refused device-column records not yet reported (settle)
 
@@ -517,6 +520,11 @@ int grow_table(fw_op* op, int new_log_r) {
     HIP_OR_RETURN(op, dmalloc(&op->cf_first, (size_t)op->table_slots));
     HIP_OR_RETURN(op, hipMemsetAsync(op->cf_first, 0xff, (size_t)op->table_slots * sizeof(uint32_t), op->stream));
   }
+  if (op->ct.nfire) {  // CountTrigger: the group starts' word per slot follows the table (written anew by every push)
+    if (op->table_slots >= (int64_t(1) << 32)) return set_err(op, FW_ERR_CAPACITY, "state table would exceed 2^32 slots");
+    dfree(op->ct.first);
+    HIP_OR_RETURN(op, dmalloc(&op->ct.first, (size_t)op->table_slots));
+  }
   if (op->dc.agg == FW_AGG_TDIGEST) {  // the compression's per-slot index follows the table
     if (op->table_slots >= (int64_t(1) << 31)) return set_err(op, FW_ERR_CAPACITY, "t-digest table would exceed 2^31 slots");
     dfree(op->td.lidx);
@@ -765,6 +773,56 @@ int push_count(fw_op* op, const int64_t* key, const int64_t* val, const int32_t*
   return snapshot(op);
 }
 
+// CountTrigger over time windows (fw_create_count_trigger): the grouped ordered pass.  The host reads three numbers
+// in the middle of the push -- the items (one per record and window that is not late), whether a region reached its
+// load limit (then the table grows and the items look their slots up again; the windows already claimed are found)
+// and the rows the push fires (for the row buffer) -- so such a push is complete when the call returns; no suspension.
+// fw_profile: the insert's rounds are timed as k_aggregate, the sort, scan and fold as k_slow (flink_window.h).
+int push_ct(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t* val, const int32_t* kh, int64_t n) {
+  int rc;
+  if ((rc = settle_quiet(op)) || (rc = maybe_restart_rows(op))) return rc;
+  if (op->dc.side_output) {
+    const int64_t rows = (int64_t)op->h_status->side_rows;
+    if ((rc = ensure_side_capacity(op, rows + n, rows))) return rc;
+  }
+  const CtBuf& t = op->ct;
+  fwdev::launch_ct_count(op->dc, op->wm, key, ts, val, kh, n, t, op->side, op->d_status, op->stream);
+  HIP_OR_RETURN(op, hipGetLastError());
+  uint32_t items = 0;
+  HIP_OR_RETURN(op, hipMemcpyAsync(&items, t.nitem + n, sizeof items, hipMemcpyDeviceToHost, op->stream));
+  HIP_OR_RETURN(op, hipStreamSynchronize(op->stream));
+  if (items) {
+    for (int round = 0;; round++) {
+      if (round > 40) return set_err(op, FW_ERR_STATE, "CountTrigger push: the state table still lacks room after 40 growths");
+      timed(op, K_AGGREGATE, [&] {
+        fwdev::launch_ct_insert(op->dc, op->wm, key, ts, kh, n, (int64_t)items, op->ct, op->tb, op->stream);
+      });
+      HIP_OR_RETURN(op, hipGetLastError());
+      unsigned long long ctr[4] = {0, 0, 0, 0};
+      HIP_OR_RETURN(op, hipMemcpyAsync(ctr, t.ctr, sizeof ctr, hipMemcpyDeviceToHost, op->stream));
+      HIP_OR_RETURN(op, hipStreamSynchronize(op->stream));
+      if (!ctr[1]) break;
+      if ((rc = grow_table(op, op->dc.log_r + 1))) return rc;
+    }
+    // rows are counted before they are written: the groups' closed-form firings, then the row buffer, then the scan
+    int half = 0;
+    timed(op, K_SLOW, [&] { half = fwdev::launch_ct_group(op->dc, (int64_t)items, op->ct, op->tb, op->stream); });
+    HIP_OR_RETURN(op, hipGetLastError());
+    unsigned long long fires = 0;
+    HIP_OR_RETURN(op, hipMemcpyAsync(&fires, t.ctr + 3, sizeof fires, hipMemcpyDeviceToHost, op->stream));
+    HIP_OR_RETURN(op, hipStreamSynchronize(op->stream));
+    const int64_t rows = (int64_t)op->h_status->out_rows;  // (settled: no kernel of this push has written a row yet)
+    if ((rc = ensure_out_capacity(op, rows + (int64_t)fires + op->table_slots, rows))) return rc;
+    timed(op, K_SLOW, [&] {
+      fwdev::launch_ct_fire(op->dc, val, (int64_t)items, op->ct, half, op->tb, op->out, op->d_status, op->stream);
+    });
+    HIP_OR_RETURN(op, hipGetLastError());
+  }
+  op->records_in += n;
+  op->push_unsettled = true;
+  return snapshot(op);
+}
+
 hipStream_t input_stream_of(const fw_op* op);  // the stream device pushes read their columns on
 // ---- timestamps at the ends of the long range (DESIGN.md "Event-time arithmetic").  The operators follow the
 // reference's wrapping longs, with three refusals (FW_ERR_TIME_RANGE), the conditions of classify's CLS_RANGE:
@@ -865,6 +923,7 @@ int push_device(fw_op* op, const int64_t* key, const int64_t* ts, const int64_t*
     return set_err(op, FW_ERR_ARG, rin ? "fw_push_row_batch needs an FW_AGG_ROW operator"
                                        : "an FW_AGG_ROW operator takes its records through fw_push_row_batch");
   if (op->cfg.assigner == FW_COUNT) return push_count(op, key, val, kh, n);
+  if (op->ct.nfire) return push_ct(op, key, ts, val, kh, n);
   int rc;
   DevCfg c = op->dc;  // by value: a session batch stamps its taint epoch into it
   // queue the batch-only kernels before waiting for the previous sequence, except with side
@@ -1066,6 +1125,12 @@ bool combine_eligible(const fw_config& c) {
   return (c.assigner == FW_TUMBLING || panes) && c.aggregate == FW_AGG_COUNT_SUM_MIN_MAX &&
          c.allowed_lateness == 0 && !c.side_output && (c.key_kind == FW_KEY_LONG || c.key_kind == FW_KEY_INT);
 }
+int combine_refuses_count(fw_op* op) {
+  return set_err(op, FW_ERR_UNSUPPORTED,
+                 "a CountTrigger handle (fw_create_count_trigger) takes no part in pre-shuffle combining: the trigger "
+                 "fires at an element in arrival order, and a combiner's partials carry no arrival order (push the "
+                 "records themselves, fw_keyby_push_device)");
+}
 int combine_refuses_continuous(fw_op* op) {
   return set_err(op, FW_ERR_UNSUPPORTED,
                  "a ContinuousEventTimeTrigger handle takes no part in pre-shuffle combining: the trigger arms a window "
@@ -1142,11 +1207,13 @@ int push_partials(fw_op* op, const PartialCols& in, int64_t n, const uint32_t* h
 // ============================================================================ C-ABI
 extern "C" {
 
-int fw_create(const fw_config* cfg_in, fw_op** out) {
-  if (!cfg_in || !out) return FW_ERR_ARG;
-  *out = nullptr;
+// fw_create (count_n = 0) and fw_create_count_trigger (count_n = CountTrigger.of's maxCount, checked by the caller)
+static int create_any(const fw_config* cfg_in, int64_t count_n, fw_op** out) {
   fw_config cfg = *cfg_in;
   char msg[256] = {0};
+  // CountTrigger over time windows keeps windows, as a ContinuousEventTimeTrigger handle does: no panes, dense
+  // regions, compact or narrow records, no single pass (its push is the grouped ordered pass, push_ct)
+  const bool counting = count_n > 0;
   // argument checks mirror the reference's constructors
   if (cfg.assigner == FW_TUMBLING) {
     if (cfg.size <= 0 || cfg.offset < 0 || cfg.offset >= cfg.size)
@@ -1316,7 +1383,7 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
   // and not for a handful of keys: a dense region's run is one workgroup's, so a few hot keys would serialise the
   // batch (C1, 170 words: k_dt_aggregate 2.4 ms per step against 0.45 ms for k_aggregate's split partitions)
   c.dense = cfg.assigner == FW_TUMBLING && cfg.aggregate == FW_AGG_COUNT_SUM_MIN_MAX && cfg.allowed_lateness == 0 &&
-            (cfg.expected_entries == 0 || cfg.expected_entries >= 65536) && !continuous &&  // (arming needs arrival
+            (cfg.expected_entries == 0 || cfg.expected_entries >= 65536) && !continuous && !counting &&  // (arming needs arrival
             !(getenv("FW_NO_DENSE") && atoi(getenv("FW_NO_DENSE")));                       // order: windows, PRec)
   int64_t s = cfg.sub_partitions;
   if (s == 0 && c.dense) {
@@ -1353,7 +1420,7 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
   // disables it)
   c.panes = cfg.assigner == FW_SLIDING && cfg.allowed_lateness == 0 && cfg.size > cfg.slide &&
             cfg.size % cfg.slide == 0 && cfg.aggregate != FW_AGG_HLL &&  // (HLL, t-digest, rows: a block per window)
-            cfg.aggregate != FW_AGG_TDIGEST && cfg.aggregate != FW_AGG_ROW && !cfg.no_panes && !continuous &&
+            cfg.aggregate != FW_AGG_TDIGEST && cfg.aggregate != FW_AGG_ROW && !cfg.no_panes && !continuous && !counting &&
             !(getenv("FW_NO_PANES") && atoi(getenv("FW_NO_PANES")));
   // windows per record, at most: ceil(size / slide), and one more for a displaced record (ts - offset + slide < 0
   // off the slide grid: Java's truncating % puts its "last start" on the grid point above ts, and
@@ -1369,7 +1436,7 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
   // and at least 2 bits of sub-partition to carry the window delta (FW_NO_COMPACT=1 disables them)
   c.compact = (cfg.assigner == FW_TUMBLING || c.panes) &&
               (cfg.aggregate == FW_AGG_COUNT_SUM_MIN_MAX || cfg.aggregate == FW_AGG_HLL ||
-               cfg.aggregate == FW_AGG_TDIGEST || cfg.aggregate == FW_AGG_ROW) && c.log_s >= 2 && !continuous &&
+               cfg.aggregate == FW_AGG_TDIGEST || cfg.aggregate == FW_AGG_ROW) && c.log_s >= 2 && !continuous && !counting &&
               !(getenv("FW_NO_COMPACT") && atoi(getenv("FW_NO_COMPACT")));
   const int64_t expected = cfg.expected_entries > 0 ? cfg.expected_entries : (int64_t)c.P * 512;
   if (cfg.aggregate >= FW_AGG_FIRST) c.agg = cfg.aggregate;  // (FW_AGG_HLL is set below)
@@ -1460,6 +1527,25 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
     HIP_OR_RETURN(op, dmalloc(&op->cf_first, (size_t)op->table_slots));
     HIP_OR_RETURN(op, hipMemsetAsync(op->cf_first, 0xff, (size_t)op->table_slots * sizeof(uint32_t), op->stream));
     HIP_OR_RETURN(op, dmalloc(&op->cf_ctr, 2));
+  }
+  if (counting) {  // the push's item buffers (no other handle has them)
+    CtBuf& t = op->ct;
+    t.nfire = count_n;
+    t.mi = mb * c.wpr;
+    if (t.mi >= (int64_t(1) << 31) || op->table_slots >= (int64_t(1) << 32))
+      return set_err(op, FW_ERR_CAPACITY, "max_batch * windows per record, or the state table, would exceed 2^31 items");
+    HIP_OR_RETURN(op, dmalloc(&t.nitem, (size_t)mb + 1));
+    HIP_OR_RETURN(op, dmalloc(&t.scan_tmp, (size_t)mb / 4096 + 1024));
+    for (int b = 0; b < 2; b++) {
+      HIP_OR_RETURN(op, dmalloc(&t.sk[b], (size_t)t.mi));
+      HIP_OR_RETURN(op, dmalloc(&t.sv[b], (size_t)t.mi));
+    }
+    HIP_OR_RETURN(op, dmalloc(&t.first, (size_t)op->table_slots));
+    HIP_OR_RETURN(op, dmalloc(&t.retry, (size_t)mb));
+    HIP_OR_RETURN(op, dmalloc(&t.ctr, 4));
+    HIP_OR_RETURN(op, dmalloc(&t.tile, (size_t)(t.mi / FW_CT_CHUNK + 2)));
+    t.tmp_bytes = fwdev::ct_sort_bytes(t.mi);
+    HIP_OR_RETURN(op, hipMalloc(&t.tmp, std::max<size_t>(t.tmp_bytes, 256)));
   }
   c.wide = op->sc[0].wide;  // (every push sets its own set's word)
   // single-pass scatter: a partition's run may take twice its share of the largest batch (part holds mb PRecs
@@ -1596,6 +1682,49 @@ int fw_create(const fw_config* cfg_in, fw_op** out) {
   return FW_OK;
 }
 
+int fw_create(const fw_config* cfg_in, fw_op** out) {
+  if (!cfg_in || !out) return FW_ERR_ARG;
+  *out = nullptr;
+  return create_any(cfg_in, 0, out);
+}
+
+// WindowedStream.trigger(CountTrigger.of(max_count)) over the aggregating state (flink_window.h "CountTrigger on the
+// aggregating operator").  Every refusal is made before the GPU is touched and names where the job runs instead.
+int fw_create_count_trigger(const fw_config* cfg_in, int64_t max_count, fw_op** out) {
+  if (!cfg_in || !out) return FW_ERR_ARG;
+  *out = nullptr;
+  char msg[320] = {0};
+  int code = FW_ERR_UNSUPPORTED;
+  if (cfg_in->trigger != FW_TRIGGER_EVENT_TIME) {
+    snprintf(msg, sizeof msg, "fw_create_count_trigger: fw_config.trigger must be 0 (the trigger is CountTrigger.of("
+                              "max_count), wrapped in PurgingTrigger by fw_config.purging); got %d", cfg_in->trigger);
+    code = FW_ERR_ARG;
+  } else if (max_count < 1 || max_count >= (int64_t(1) << 31)) {
+    snprintf(msg, sizeof msg, "CountTrigger maxCount must be in [1, 2^31), got %lld", (long long)max_count);
+    code = FW_ERR_ARG;
+  } else if (cfg_in->assigner == FW_SESSION) {
+    snprintf(msg, sizeof msg, "CountTrigger over session windows is not offered on the aggregating operator (the "
+                              "merged sessions' counts follow the merges in arrival order): the window-contents "
+                              "operator takes it with merging_state (fw_list_create, GpuListWindowOperator)");
+  } else if (cfg_in->assigner == FW_COUNT) {
+    snprintf(msg, sizeof msg, "CountTrigger over count windows: countWindow(size, slide) is FW_COUNT through fw_create "
+                              "already; GlobalWindows with this trigger and another function run on the "
+                              "window-contents operator (fw_list_create)");
+  } else if (cfg_in->aggregate != FW_AGG_COUNT_SUM_MIN_MAX) {
+    snprintf(msg, sizeof msg, "CountTrigger is offered for the count/sum/min/max aggregate (FW_AGG_COUNT_SUM_MIN_MAX); "
+                              "aggregate %d under this trigger runs on the window-contents operator (fw_list_create, "
+                              "GpuListWindowOperator)", cfg_in->aggregate);
+  }
+  if (msg[0]) {
+    fw_op* op = new fw_op();
+    op->cfg = *cfg_in;
+    op->err = msg;
+    *out = op;
+    return code;
+  }
+  return create_any(cfg_in, max_count, out);
+}
+
 void fw_destroy(fw_op* op) {
   if (!op) return;
   if (op->stream) {
@@ -1697,6 +1826,17 @@ void fw_destroy(fw_op* op) {
   dfree(op->d_disp);
   dfree(op->cf_first);
   dfree(op->cf_ctr);
+  dfree(op->ct.nitem);
+  dfree(op->ct.scan_tmp);
+  for (int b = 0; b < 2; b++) {
+    dfree(op->ct.sk[b]);
+    dfree(op->ct.sv[b]);
+  }
+  dfree(op->ct.first);
+  dfree(op->ct.retry);
+  dfree(op->ct.ctr);
+  dfree(op->ct.tile);
+  if (op->ct.tmp) (void)hipFree(op->ct.tmp);
   for (auto& pr : op->prof_pending) {
     (void)hipEventDestroy(pr.a);
     (void)hipEventDestroy(pr.b);
@@ -1738,7 +1878,7 @@ namespace {
 // the stream a device push reads its columns on: the input stream when async input applies to the operator's
 // batches (push_device's `two`: not with side output or count windows)
 hipStream_t input_stream_of(const fw_op* op) {
-  const bool two = op->async_in && !op->dc.side_output && op->cfg.assigner != FW_COUNT;
+  const bool two = op->async_in && !op->dc.side_output && op->cfg.assigner != FW_COUNT && !op->ct.nfire;
   return two ? op->bstream : op->stream;
 }
 
@@ -2022,6 +2162,8 @@ int fw_get_stats(fw_op* op, fw_stats* o) {
   HIP_OR_RETURN(op, hipMemsetAsync(op->d_stats3, 0, 4 * sizeof(unsigned long long), op->stream));
   if (cont_iv(op->dc))
     fwdev::launch_cont_stats(op->dc, op->tb, op->d_stats3, op->stream);
+  else if (op->ct.nfire)
+    fwdev::launch_ct_stats(op->dc, op->tb, op->d_stats3, op->stream);
   else
     fwdev::launch_table_stats(op->dc, op->tb, op->d_stats3, op->stream);
   unsigned long long h3[4];
@@ -2078,6 +2220,7 @@ int fw_combine_extract_device(fw_op* op, int32_t world, fw_partials* out, int64_
                               int64_t* n) {
   if (!op || !n || world < 1 || (world > 1 && !counts)) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
   if (cont_iv(op->dc)) return combine_refuses_continuous(op);
+  if (op->ct.nfire) return combine_refuses_count(op);
   if (!combine_eligible(op->cfg))
     return set_err(op, FW_ERR_UNSUPPORTED,
                    "combining needs tumbling windows or sliding windows kept as panes, the count/sum/min/max aggregate, no "
@@ -2131,6 +2274,7 @@ static int fw_combine_extract_device_any(fw_op* op, int32_t world, fw_partials* 
 int fw_push_partials_device(fw_op* op, const fw_partials* in, int64_t n) {
   if (!op || !in || n < 0) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
   if (cont_iv(op->dc)) return combine_refuses_continuous(op);
+  if (op->ct.nfire) return combine_refuses_count(op);
   if (!combine_eligible(op->cfg))
     return set_err(op, FW_ERR_UNSUPPORTED,
                    "combining needs tumbling windows or sliding windows kept as panes, the count/sum/min/max aggregate, no "
@@ -2331,16 +2475,29 @@ int fw_snapshot_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* dst
   if (op && cont_iv(op->dc))
     return set_err(op, FW_ERR_UNSUPPORTED, "a ContinuousEventTimeTrigger handle's windows carry the trigger's fire time "
                                            "and its timer: use fw_snapshot_key_group_fire");
+  if (op && op->ct.nfire)
+    return set_err(op, FW_ERR_UNSUPPORTED, "a CountTrigger handle's windows carry the trigger's count: use "
+                                           "fw_snapshot_key_group_trigger_count");
   return snapshot_rows_any(op, kg, dst, blocks, nullptr, cap, n);
 }
+int fw_snapshot_key_group_trigger_count(fw_op* op, int32_t kg, const fw_state_rows* dst, int64_t* tcount, int64_t cap,
+                                        int64_t* n) {
+  if (op && !op->ct.nfire)
+    return set_err(op, FW_ERR_UNSUPPORTED, "fw_snapshot_key_group_trigger_count needs a handle of "
+                                           "fw_create_count_trigger (others: fw_snapshot_key_group, "
+                                           "fw_snapshot_key_group_blocks, fw_snapshot_key_group_fire)");
+  if (op && dst && cap > 0 && !tcount) return set_err(op, FW_ERR_ARG, "null trigger_count column");
+  return snapshot_rows_any(op, kg, dst, nullptr, tcount, cap, n);
+}
 int fw_snapshot_key_group_fire(fw_op* op, int32_t kg, const fw_state_rows* dst, int64_t* fire, int64_t cap, int64_t* n) {
-  if (op && !cont_iv(op->dc))
+  if (op && (!cont_iv(op->dc) || op->ct.nfire))
     return set_err(op, FW_ERR_UNSUPPORTED, "fw_snapshot_key_group_fire needs a FW_TRIGGER_CONTINUOUS_EVENT_TIME handle "
                                            "(others: fw_snapshot_key_group, fw_snapshot_key_group_blocks)");
   if (op && dst && cap > 0 && !fire) return set_err(op, FW_ERR_ARG, "null fire_time column");
   return snapshot_rows_any(op, kg, dst, nullptr, fire, cap, n);
 }
-// the rows of key group kg (fire != NULL: a ContinuousEventTimeTrigger handle's, with their fire times)
+// the rows of key group kg (fire != NULL: a ContinuousEventTimeTrigger handle's, with their fire times, or a
+// CountTrigger handle's, with their trigger counts)
 static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, uint8_t* blocks, int64_t* fire,
                              int64_t cap, int64_t* n) {
   if (op && op->cfg.assigner == FW_COUNT)
@@ -2363,7 +2520,8 @@ static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, ui
   StateCols d{};
   uint8_t* acc = nullptr;
   int64_t* dfire = nullptr;
-  const bool cont = cont_iv(c) != 0;
+  const bool ct = op->ct.nfire != 0;
+  const bool cont = cont_iv(c) != 0 || ct;  // (an extra column beside the rows)
   auto release = [&]() {
     free_state_cols(d);
     dfree(d.blk);
@@ -2377,7 +2535,9 @@ static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, ui
     return rc == FW_ERR_HIP ? set_err(op, rc, "snapshot: allocation failed") : rc;
   }
   HIP_OR_RETURN(op, hipMemsetAsync(op->d_stats3, 0, sizeof(unsigned long long), op->stream));
-  if (cont)
+  if (ct)
+    fwdev::launch_ct_snapshot(c, op->tb, p0, np, d, dfire, op->d_stats3, op->stream);
+  else if (cont)
     fwdev::launch_cont_snapshot(c, op->tb, p0, np, d, dfire, op->d_stats3, op->stream);
   else
     fwdev::launch_snapshot(c, op->tb, p0, np, d, op->d_stats3, op->stream);
@@ -2476,10 +2636,22 @@ int fw_restore_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* src,
   if (op && cont_iv(op->dc))
     return set_err(op, FW_ERR_UNSUPPORTED, "a ContinuousEventTimeTrigger handle's windows carry the trigger's fire time "
                                            "and its timer: use fw_restore_key_group_fire");
+  if (op && op->ct.nfire)
+    return set_err(op, FW_ERR_UNSUPPORTED, "a CountTrigger handle's windows carry the trigger's count: use "
+                                           "fw_restore_key_group_trigger_count");
   return restore_rows_any(op, kg, src, blocks, nullptr, n);
 }
+int fw_restore_key_group_trigger_count(fw_op* op, int32_t kg, const fw_state_rows* src, const int64_t* tcount,
+                                       int64_t n) {
+  if (op && !op->ct.nfire)
+    return set_err(op, FW_ERR_UNSUPPORTED, "fw_restore_key_group_trigger_count needs a handle of "
+                                           "fw_create_count_trigger (others: fw_restore_key_group, "
+                                           "fw_restore_key_group_blocks, fw_restore_key_group_fire)");
+  if (op && n > 0 && !tcount) return set_err(op, FW_ERR_ARG, "null trigger_count column");
+  return restore_rows_any(op, kg, src, nullptr, tcount, n);
+}
 int fw_restore_key_group_fire(fw_op* op, int32_t kg, const fw_state_rows* src, const int64_t* fire, int64_t n) {
-  if (op && !cont_iv(op->dc))
+  if (op && (!cont_iv(op->dc) || op->ct.nfire))
     return set_err(op, FW_ERR_UNSUPPORTED, "fw_restore_key_group_fire needs a FW_TRIGGER_CONTINUOUS_EVENT_TIME handle "
                                            "(others: fw_restore_key_group, fw_restore_key_group_blocks)");
   if (op && n > 0 && !fire) return set_err(op, FW_ERR_ARG, "null fire_time column");
@@ -2500,6 +2672,16 @@ static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, con
   const int64_t* hs[8] = {src->key, src->start, src->end, src->count, src->sum, src->min, src->max, src->timer};
   for (const int64_t* h : hs)
     if (!h) return set_err(op, FW_ERR_ARG, "null state column");
+  const bool ct = op->ct.nfire != 0;
+  if (ct) {  // the rows as fw_snapshot_key_group_trigger_count writes them, checked before anything changes
+    for (int64_t i = 0; i < n; i++) {
+      if (src->count[i] < 0 || src->end[i] != (int64_t)((uint64_t)src->start[i] + (uint64_t)op->dc.size))
+        return set_err(op, FW_ERR_ARG, "restore: row %lld is not a window of this operator's size", (long long)i);
+      if (fire[i] < 0 || fire[i] >= (int64_t(1) << 48))
+        return set_err(op, FW_ERR_ARG, "restore: row %lld: trigger count %lld is not in [0, 2^48)", (long long)i,
+                       (long long)fire[i]);
+    }
+  }
   const bool cont = cont_iv(op->dc) != 0;
   if (cont) {  // the rows as fw_snapshot_key_group_fire writes them, checked before anything changes
     const int64_t iv = cont_iv(op->dc);
@@ -2562,7 +2744,7 @@ static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, con
   for (int i = 0; i < 8; i++)
     if (hipMemcpyAsync(ds[i], hs[i], n * sizeof(int64_t), hipMemcpyHostToDevice, op->stream) != hipSuccess)
       return fail(set_err(op, FW_ERR_HIP, "restore: copy failed"));
-  if (cont && (dmalloc(&dfire, (size_t)n) != hipSuccess ||
+  if ((cont || ct) && (dmalloc(&dfire, (size_t)n) != hipSuccess ||
                hipMemcpyAsync(dfire, fire, n * sizeof(int64_t), hipMemcpyHostToDevice, op->stream) != hipSuccess))
     return fail(set_err(op, FW_ERR_HIP, "restore: copy failed"));
   // the rows' demand per partition: grow the table first if a region would pass its load limit
@@ -2618,7 +2800,9 @@ static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, con
         hipMemcpyAsync(d_round, round_of.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, op->stream) != hipSuccess)
       return fail(set_err(op, FW_ERR_HIP, "restore: allocation failed"));
   }
-  if (cont)
+  if (ct)
+    fwdev::launch_ct_restore(op->dc, kg, d, dfire, n, op->tb, op->d_status, d_round, rounds, op->stream);
+  else if (cont)
     fwdev::launch_cont_restore(op->dc, kg, d, dfire, n, op->tb, op->d_status, d_round, rounds, op->stream);
   else
     fwdev::launch_restore(op->dc, kg, d, n, nullptr, op->tb, op->d_status, d_round, rounds, op->stream);
@@ -3086,6 +3270,7 @@ int fw_keyby_combine_push_device(fw_comm* c, fw_op* comb, fw_op* op, const int64
       return set_err(op, FW_ERR_ARG, "the operator's KeyGroupRange is not subtask %d of %d's", r, W);
   }
   if (cont_iv(op->dc) || cont_iv(comb->dc)) return combine_refuses_continuous(op);
+  if (op->ct.nfire || comb->ct.nfire) return combine_refuses_count(op);
   if (combine_config_tag(comb->cfg) != combine_config_tag(op->cfg))
     return set_err(op, FW_ERR_ARG,
                    "the combiner is configured differently (assigner, size, offset, value type, key kind, max "

@@ -17,7 +17,8 @@ import numpy as np
 
 from . import _native as N
 from .keygroups import KeyGroupRange
-from .windowing import ContinuousEventTimeTrigger, CountSumMinMax, EventTimeTrigger, Trigger, WindowAssigner
+from .windowing import (ContinuousEventTimeTrigger, CountSumMinMax, CountTrigger, EventTimeTrigger, Trigger,
+                        WindowAssigner)
 
 ROW_FIELDS = ("key", "start", "end", "count", "sum", "min", "max")
 ROW_DTYPE = np.dtype([(f, "<i8") for f in ROW_FIELDS] + [("epoch", "<i8")])
@@ -27,6 +28,8 @@ STATE_DTYPE = np.dtype([(f, "<i8") for f in STATE_FIELDS])
 # maxTimestamp's timer, bit 1 = the timer at the fire time (fw_snapshot_key_group_fire)
 FIRE_STATE_DTYPE = np.dtype(STATE_DTYPE.descr + [("fire_time", "<i8")])
 FIRE_NULL = -(1 << 63)
+# CountTrigger handles: the trigger's count per window (fw_snapshot_key_group_trigger_count)
+COUNT_STATE_DTYPE = np.dtype(STATE_DTYPE.descr + [("trigger_count", "<i8")])
 SIDE_DTYPE = np.dtype([("key", "<i8"), ("ts", "<i8"), ("val", "<i8"), ("epoch", "<i8")])
 # list state per key group (fw_list_state): the lists and their elements concatenated in list order.  Snapshots of
 # GpuListWindowOperator (listwindow.py takes the two from here) and of a count-window GpuWindowOperator
@@ -53,9 +56,10 @@ class GpuWindowOperator:
                  sub_partitions=0, async_input=True, no_panes=False):
         trigger = trigger or EventTimeTrigger.create()
         inner = getattr(trigger, "nested", trigger)
-        if not isinstance(inner, (EventTimeTrigger, ContinuousEventTimeTrigger)):
-            raise ValueError("GpuWindowOperator takes EventTimeTrigger, ContinuousEventTimeTrigger.of(interval) or "
-                             "PurgingTrigger.of(either); count triggers run on GpuListWindowOperator")
+        if not isinstance(inner, (EventTimeTrigger, ContinuousEventTimeTrigger, CountTrigger)):
+            raise ValueError("GpuWindowOperator takes EventTimeTrigger, ContinuousEventTimeTrigger.of(interval), "
+                             "CountTrigger.of(n) or PurgingTrigger.of(one of them); other triggers run on "
+                             "GpuListWindowOperator")
         if allowed_lateness < 0:
             raise ValueError("The allowed lateness cannot be negative.")
         kgr = key_group_range or KeyGroupRange(0, max_parallelism - 1)
@@ -108,7 +112,13 @@ class GpuWindowOperator:
         self._cfg = c
         self._h = ctypes.c_void_p()
         L = N.lib()
-        rc = L.fw_create(ctypes.byref(c), ctypes.byref(self._h))
+        # CountTrigger.of(n) over the aggregating state: a constructor of its own (fw_config does not grow); it refuses
+        # sessions, count windows and every aggregate but count/sum/min/max and names GpuListWindowOperator
+        self._counting = isinstance(inner, CountTrigger)
+        if self._counting:
+            rc = L.fw_create_count_trigger(ctypes.byref(c), int(inner.count), ctypes.byref(self._h))
+        else:
+            rc = L.fw_create(ctypes.byref(c), ctypes.byref(self._h))
         if rc != N.FW_OK:
             msg = L.fw_last_error(self._h).decode() if self._h else "fw_create failed"
             L.fw_destroy(self._h)
@@ -515,6 +525,8 @@ class GpuWindowOperator:
         bytes: HyperLogLog registers / the t-digest's centroids) for the HyperLogLog and t-digest aggregates."""
         if self._continuous:  # the trigger's fire time rides with the window (fw_snapshot_key_group_fire)
             return FIRE_STATE_DTYPE
+        if self._counting:  # the trigger's count (fw_snapshot_key_group_trigger_count)
+            return COUNT_STATE_DTYPE
         bb = N.lib().fw_state_block_bytes(self._h)
         return STATE_DTYPE if bb == 0 else np.dtype(STATE_DTYPE.descr + [("acc", "u1", (bb,))])
 
@@ -540,15 +552,17 @@ class GpuWindowOperator:
             for f in ec:
                 el[f] = ec[f]
             return lists, el
-        if self._continuous:
+        if self._continuous or self._counting:
+            extra = "fire_time" if self._continuous else "trigger_count"
+            snap = L.fw_snapshot_key_group_fire if self._continuous else L.fw_snapshot_key_group_trigger_count
             n = ctypes.c_int64()
-            N.check(L.fw_snapshot_key_group_fire(self._h, int(kg), None, None, 0, ctypes.byref(n)), self._h)
-            cols = {f: np.zeros(n.value, dtype=np.int64) for f in STATE_FIELDS + ("fire_time",)}
+            N.check(snap(self._h, int(kg), None, None, 0, ctypes.byref(n)), self._h)
+            cols = {f: np.zeros(n.value, dtype=np.int64) for f in STATE_FIELDS + (extra,)}
             dst = N.FwStateRows(**{f: cols[f].ctypes.data for f in STATE_FIELDS})
             got = ctypes.c_int64()
-            N.check(L.fw_snapshot_key_group_fire(self._h, int(kg), ctypes.byref(dst), cols["fire_time"].ctypes.data,
-                                                 n.value, ctypes.byref(got)), self._h)
-            out = np.zeros(got.value, dtype=FIRE_STATE_DTYPE)
+            N.check(snap(self._h, int(kg), ctypes.byref(dst), cols[extra].ctypes.data, n.value, ctypes.byref(got)),
+                    self._h)
+            out = np.zeros(got.value, dtype=self.state_dtype())
             for f in cols:
                 out[f] = cols[f][:got.value]
             return out
@@ -588,14 +602,15 @@ class GpuWindowOperator:
             return
         if elems is not None:
             raise ValueError("only count windows restore (lists, elems); this operator restores state_dtype() rows")
-        if self._continuous:
+        if self._continuous or self._counting:
+            extra = "fire_time" if self._continuous else "trigger_count"
+            restore = L.fw_restore_key_group_fire if self._continuous else L.fw_restore_key_group_trigger_count
             rows = np.ascontiguousarray(rows)
-            if rows.dtype.names is None or "fire_time" not in rows.dtype.names:
-                raise ValueError("rows of a ContinuousEventTimeTrigger operator carry `fire_time` (state_dtype())")
-            cols = {f: np.ascontiguousarray(rows[f], dtype=np.int64) for f in STATE_FIELDS + ("fire_time",)}
+            if rows.dtype.names is None or extra not in rows.dtype.names:
+                raise ValueError(f"rows of this operator carry `{extra}` (state_dtype())")
+            cols = {f: np.ascontiguousarray(rows[f], dtype=np.int64) for f in STATE_FIELDS + (extra,)}
             src = N.FwStateRows(**{f: cols[f].ctypes.data for f in STATE_FIELDS})
-            N.check(L.fw_restore_key_group_fire(self._h, int(kg), ctypes.byref(src), cols["fire_time"].ctypes.data,
-                                                len(rows)), self._h)
+            N.check(restore(self._h, int(kg), ctypes.byref(src), cols[extra].ctypes.data, len(rows)), self._h)
             return
         bb = L.fw_state_block_bytes(self._h)
         rows = np.ascontiguousarray(rows)

@@ -158,7 +158,7 @@ class EventTimeTrigger(Trigger):
 
 class PurgingTrigger(Trigger):
     """PurgingTrigger.of(EventTimeTrigger.create()) (PurgingTrigger.java:45-59); around
-    ContinuousEventTimeTrigger.of(interval) for both operators, around CountTrigger.of(n) or DeltaTrigger.of(threshold)
+    ContinuousEventTimeTrigger.of(interval) or CountTrigger.of(n) for both operators, around DeltaTrigger.of(threshold)
     for the window-contents operator only."""
     purging = True
 
@@ -190,7 +190,9 @@ class GlobalWindows(WindowAssigner):
 
 
 class CountTrigger(Trigger):
-    """CountTrigger.of(n) (CountTrigger.java:47-70): FIRE at every n-th element of a (key, window)."""
+    """CountTrigger.of(n) (CountTrigger.java:47-70): FIRE at every n-th element of a (key, window).  For the
+    window-contents operator (GpuListWindowOperator) and, with the count/sum/min/max aggregate over tumbling and sliding
+    windows, for the aggregating operator (GpuWindowOperator, fw_create_count_trigger)."""
 
     def __init__(self, count):
         if count <= 0:

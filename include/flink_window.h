@@ -338,7 +338,9 @@ int fw_get_stats(fw_op* op, fw_stats* out);
  * classify_hist, scan, scatter, aggregate, slow, fire, tdigest (the t-digest compression of a push).  fw_profile_read returns accumulated
  * milliseconds and launch counts per kind (arrays of FW_NUM_KERNELS) and optionally resets them.
  * enable: 0 = off, 1 = every kind, FW_PROFILE_KINDS | (1 << kind) | ... = only those kinds (each timed launch
- * adds two event markers to its stream, so a measurement that needs one kernel's duration times only that one). */
+ * adds two event markers to its stream, so a measurement that needs one kernel's duration times only that one).
+ * A handle of fw_create_count_trigger has no aggregate or ordered path of that form: it reports its slot lookup under
+ * k_aggregate and its sort, scan and fold under k_slow; classify_hist, scan and scatter stay 0. */
 #define FW_NUM_KERNELS 7
 #define FW_PROFILE_KINDS 0x100
 int fw_profile(fw_op* op, int enable);
@@ -448,6 +450,41 @@ int fw_snapshot_key_group_fire(fw_op* op, int32_t key_group, const fw_state_rows
                                int64_t cap, int64_t* n);
 int fw_restore_key_group_fire(fw_op* op, int32_t key_group, const fw_state_rows* host_src,
                               const int64_t* host_fire_time, int64_t n);
+
+/* CountTrigger on the aggregating operator: WindowedStream.trigger(CountTrigger.of(max_count)) over the aggregating
+ * state (WindowOperator.java:379-407 with HeapAggregatingState; CountTrigger.java:47-85), `cfg->purging` wrapping it
+ * in PurgingTrigger.  A second constructor, as fw_list_create_join is: fw_config does not grow, cfg->trigger must be 0
+ * (FW_ERR_ARG), and fw_create goes on refusing FW_TRIGGER_COUNT.
+ *   Per element and window that is not late (cleanupTime > watermark; a window behind the watermark but within the
+ *   allowed lateness counts like any other -- this trigger has no late firing of its own): add the element, count += 1,
+ *   and at count >= max_count clear the count and emit one row {count, sum, min, max} of the accumulator as of that
+ *   element; under PurgingTrigger the accumulator is cleared behind the row.  The comparison is >=: a restored or merged
+ *   count of max_count or more fires at the next element.  A watermark fires nothing (onEventTime: CONTINUE); at the
+ *   cleanup time the accumulator and the count are dropped, so a window's last < max_count elements are never emitted.
+ *   Late records (all windows late): side output / late_records_dropped as on every handle.
+ *   Offered for FW_AGG_COUNT_SUM_MIN_MAX over every value type and key kind, FW_TUMBLING and FW_SLIDING, with allowed
+ *   lateness, purging and side output, host and device pushes.  The handle keeps windows (no panes, dense regions,
+ *   compact or narrow records, single pass); the count rides in the window's entry.  A push, device columns included,
+ *   is complete when the call returns (the host reads the push's row bound in the middle of it), and
+ *   fw_input_stream(op) == fw_stream(op) whatever fw_set_async_input says.
+ *   Refused before the GPU is touched: max_count outside [1, 2^31) and cfg->trigger != 0 (FW_ERR_ARG); FW_SESSION
+ *   (fw_list_create with merging_state takes CountTrigger over sessions), FW_COUNT and every other aggregate
+ *   (FW_ERR_UNSUPPORTED; each message names fw_list_create).
+ *   Every entry point takes such a handle except the pre-shuffle combiner ones (a combiner's partials carry no arrival
+ *   order) and the other snapshot / restore calls, which name the pair below (FW_ERR_UNSUPPORTED).
+ *   fw_stats: keyed_state_entries counts the windows with contents (a purged window keeps its emptied entry and its
+ *   cleanup timer until the cleanup time), event_time_timers one cleanup timer per window in flight.
+ * fw_snapshot_key_group_trigger_count / fw_restore_key_group_trigger_count: the rows of fw_snapshot_key_group plus
+ *   trigger_count[i], row i's count state (CountTrigger's "count" ReducingState, Sum; in [0, 2^48)); `timer` is 0 (no
+ *   timer at maxTimestamp).  A purged, empty window is a row of count 0 until its cleanup time.  Restore into any
+ *   KeyGroupRange works as for the plain rows; rows of one (key, window) merge and their trigger counts add without
+ *   firing (CountTrigger.onMerge).  These two refuse every other handle.  (The heap-format bridge does not carry this
+ *   state: DESIGN.md §7.) */
+int fw_create_count_trigger(const fw_config* cfg, int64_t max_count, fw_op** out);
+int fw_snapshot_key_group_trigger_count(fw_op* op, int32_t key_group, const fw_state_rows* host_dst,
+                                        int64_t* host_trigger_count, int64_t cap, int64_t* n);
+int fw_restore_key_group_trigger_count(fw_op* op, int32_t key_group, const fw_state_rows* host_src,
+                                       const int64_t* host_trigger_count, int64_t n);
 
 /* Key routing (both sides of keyBy).
  *   fw_key_groups_device: kg[i] = KeyGroupRangeAssignment.assignToKeyGroup(key_i, maxParallelism)

@@ -44,6 +44,7 @@ def main():
     ap.add_argument("--merging-state", action="store_true",
                     help="with --sessions: the handle keeps the MergingWindowSet form (implied by --trigger count:N)")
     ap.add_argument("--interval", type=int, default=250, help="ContinuousEventTimeTrigger's interval, ms")
+    ap.add_argument("--purging", action="store_true", help="wrap the trigger in PurgingTrigger")
     ap.add_argument("--cpu-sample", type=int, default=1 << 22)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     args = ap.parse_args()
@@ -72,6 +73,9 @@ def main():
         trig = ContinuousEventTimeTrigger.of(args.interval) if args.trigger == "continuous" else None
     else:
         ap.error("--trigger: event_time, continuous, count:N or delta")
+    if args.purging:
+        from flink_amd import EventTimeTrigger, PurgingTrigger
+        trig = PurgingTrigger.of(trig if trig is not None else EventTimeTrigger.create())
     if trig is not None:
         args.no_cpu_baseline = True  # (the ListState oracle has neither trigger: no CPU leg for them)
     assigner = EventTimeSessionWindows.with_gap(args.sessions) if args.sessions else TumblingEventTimeWindows.of(args.window)
