@@ -29,4 +29,7 @@ def __getattr__(name):
     if name in ("GpuWindowJoin", "PAIR_DTYPE"):
         from . import join
         return getattr(join, name)
+    if name in ("OverAggregate", "Over"):
+        from . import over
+        return getattr(over, name)
     raise AttributeError(name)

@@ -153,6 +153,34 @@ class FwSessionState(ctypes.Structure):
                                                "timer", "n_elems", "ts", "val", "ordinal")]
 
 
+FW_OVER_BOUNDED_ROWS, FW_OVER_BOUNDED_RANGE, FW_OVER_UNBOUNDED_ROWS, FW_OVER_UNBOUNDED_RANGE = 0, 1, 2, 3
+
+
+class FwOverConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "key_kind", "max_parallelism", "key_group_start",
+                                              "key_group_end", "device", "row_columns", "row_aggregates")] + \
+        [("row_column_type", ctypes.c_int32 * 8), ("row_aggregate", ctypes.c_int32 * 16)] + \
+        [(n, ctypes.c_int64) for n in ("preceding", "expected_keys", "max_batch")]
+
+
+class FwOverRows(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("key", "rowtime", "ordinal", "values", "null_mask")]
+
+
+class FwOverStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("rows_kept", "late_rows_dropped", "keys", "retained_rows",
+                                              "pending_rows", "current_watermark", "fired_rows_total",
+                                              "pending_output_rows")]
+
+
+class FwOverState(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("key", "last_ts", "acc", "n_rows", "ts", "ordinal", "cols", "nulls")]
+
+
+def fw_over_acc_words(columns):
+    return 1 + 5 * columns
+
+
 # every exported symbol with its ctypes signature (restype, argtypes); mirrors include/flink_window.h
 SIGNATURES = {
     "fw_create": (ctypes.c_int, [ctypes.POINTER(FwConfig), ctypes.POINTER(VP)]),
@@ -257,6 +285,20 @@ SIGNATURES = {
                                                    ctypes.c_int64, I64P, I64P]),
     "fw_count_restore_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwListState), ctypes.c_int64,
                                                   ctypes.c_int64]),
+    "fw_over_create": (ctypes.c_int, [ctypes.POINTER(FwOverConfig), ctypes.POINTER(VP)]),
+    "fw_over_destroy": (None, [VP]),
+    "fw_over_last_error": (ctypes.c_char_p, [VP]),
+    "fw_over_push_batch": (ctypes.c_int, [VP, VP, VP, VP, VP, VP, ctypes.c_int64]),
+    "fw_over_push_batch_device": (ctypes.c_int, [VP, VP, VP, VP, VP, VP, ctypes.c_int64]),
+    "fw_over_advance_watermark": (ctypes.c_int, [VP, ctypes.c_int64, I64P]),
+    "fw_over_drain": (ctypes.c_int, [VP, ctypes.POINTER(FwOverRows), VP, ctypes.c_int64, I64P]),
+    "fw_over_rows_device": (ctypes.c_int, [VP, ctypes.POINTER(FwOverRows), I64P]),
+    "fw_over_clear_pending": (ctypes.c_int, [VP]),
+    "fw_over_get_stats": (ctypes.c_int, [VP, ctypes.POINTER(FwOverStats)]),
+    "fw_over_snapshot_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwOverState), ctypes.c_int64,
+                                                  ctypes.c_int64, I64P, I64P]),
+    "fw_over_restore_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwOverState), ctypes.c_int64,
+                                                 ctypes.c_int64]),
     "fw_generate_device": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, VP,
                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, VP, VP, VP, VP, VP]),
 }

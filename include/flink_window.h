@@ -941,6 +941,116 @@ int fw_generate_device(uint64_t seed, int64_t first, int64_t n, int64_t num_keys
                        int64_t ts_base, int64_t rate, int64_t jitter, int64_t* key, int64_t* ts, int64_t* val,
                        int64_t* max_ts, void* stream);
 
+/* ---- Table API OVER windows on row time (fw_over.hip) ----
+ * Paths below are relative to flink-libraries/flink-table/src/main/scala/org/apache/flink/table/ ("FT/").  The handle
+ * replaces the four ProcessFunctions that FT/plan/nodes/datastream/DataStreamOverAggregate.scala:252-275 builds for
+ * `agg OVER (PARTITION BY k ORDER BY rowtime ROWS | RANGE BETWEEN x PRECEDING AND CURRENT ROW)`: one output row per
+ * input row, carrying the row's key, row time and arrival ordinal (the host re-attaches the forwarded fields by
+ * ordinal) and the aggregates over the row's frame. */
+#define FW_OVER_BOUNDED_ROWS 0    /* ROWS BETWEEN preceding PRECEDING AND CURRENT ROW (RowTimeBoundedRowsOver)      */
+#define FW_OVER_BOUNDED_RANGE 1   /* RANGE BETWEEN preceding (ms) PRECEDING AND CURRENT ROW (RowTimeBoundedRangeOver) */
+#define FW_OVER_UNBOUNDED_ROWS 2  /* ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW (RowTimeUnboundedRowsOver)    */
+#define FW_OVER_UNBOUNDED_RANGE 3 /* RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW (RowTimeUnboundedRangeOver)  */
+
+typedef struct fw_over fw_over;
+typedef struct fw_over_config {
+  int32_t kind;                /* FW_OVER_* */
+  int32_t key_kind;            /* FW_KEY_* */
+  int32_t max_parallelism;
+  int32_t key_group_start;     /* the handle's KeyGroupRange, inclusive */
+  int32_t key_group_end;
+  int32_t device;
+  int32_t row_columns;         /* value columns per row, 1 .. 8 (FW_AGG_ROW's encoding)            */
+  int32_t row_aggregates;      /* aggregates per output row, 1 .. 16                                */
+  int32_t row_column_type[8];  /* FW_VAL_* of each column                                           */
+  int32_t row_aggregate[16];   /* FW_ROW_* << 8 | column                                            */
+  int64_t preceding;           /* ROWS: N in [0, 2^31); RANGE: t >= 0 ms; ignored by unbounded kinds */
+  int64_t expected_keys;       /* sizes the key map at creation (it grows); 0 = default             */
+  int64_t max_batch;           /* largest push; 0 = default                                         */
+} fw_over_config;
+
+/* output rows: values[i * row_aggregates + s] (integers sign-extended, Double results as f64 bits), null_mask[i]
+ * bit s = aggregate s is NULL */
+typedef struct fw_over_rows {
+  int64_t* key;
+  int64_t* rowtime;
+  int64_t* ordinal;
+  int64_t* values;
+  uint32_t* null_mask;
+} fw_over_rows;
+
+typedef struct fw_over_stats {
+  int64_t rows_kept;          /* pushed rows stored                                                  */
+  int64_t late_rows_dropped;  /* pushed rows dropped as late (no side output in the reference)       */
+  int64_t keys;               /* keys with state                                                     */
+  int64_t retained_rows;      /* fired rows kept for later frames (bounded kinds)                    */
+  int64_t pending_rows;       /* stored rows that have not fired                                     */
+  int64_t current_watermark;
+  int64_t fired_rows_total;
+  int64_t pending_output_rows;
+} fw_over_stats;
+
+/* keyed state of one key group.  Per key: last_ts = lastTriggeringTs (bounded kinds; 0 otherwise), acc = the unbounded
+ * kinds' accumulator Row as FW_OVER_ACC_WORDS(row_columns) words: the rows accumulated, then per column its non-null
+ * count, the sum's low and high words (Double: the f64 sum, 0), min and max (0 when the count is 0); zeros for the
+ * bounded kinds, whose accumulators are functions of the retained rows.  n_rows[i] rows of key i follow each other in
+ * the row columns (retained and pending rows in arrival order): cols[r * row_columns + j], nulls[r] bit j. */
+#define FW_OVER_ACC_WORDS(columns) (1 + 5 * (columns))
+typedef struct fw_over_state {
+  int64_t* key;
+  int64_t* last_ts;
+  int64_t* acc;
+  int64_t* n_rows;
+  int64_t* ts;
+  int64_t* ordinal;
+  int64_t* cols;
+  uint8_t* nulls;
+} fw_over_state;
+
+/* open() of the ProcessFunction.  Refused before the GPU is touched: an unknown kind, ROWS preceding outside
+ * [0, 2^31), RANGE preceding < 0, zero or too many columns / aggregates, a bad key group range (FW_ERR_ARG); Float
+ * SUM / AVG (FW_ERR_UNSUPPORTED: the reference rounds to float after every accumulate and retract).  A failed create
+ * returns a handle that carries the message (fw_over_last_error) and must be destroyed. */
+int fw_over_create(const fw_over_config* cfg, fw_over** out);
+void fw_over_destroy(fw_over* op);
+/* the handle's last message.  fw_last_error takes an fw_op and does not serve an fw_over (as fw_list_last_error) */
+const char* fw_over_last_error(const fw_over* op);
+/* processElement (RowTimeBoundedRangeOver.scala:109-138, RowTimeBoundedRowsOver.scala:118-147,
+ * RowTimeUnboundedOver.scala:103-129) for n rows: a bounded kind keeps a row iff rowtime > the key's
+ * lastTriggeringTs (0 for a fresh key), an unbounded kind iff rowtime > the current watermark; other rows are dropped
+ * and counted.  Row i of the push gets arrival ordinal (rows pushed so far) + i, dropped rows included.  cols:
+ * column-major (cols + j * n = column j), nulls: bit j of nulls[i] = column j is NULL (NULL = none).  A
+ * Long.MIN_VALUE row time: FW_ERR_NO_TIMESTAMP; a key outside the KeyGroupRange: FW_ERR_KEY_GROUP; rows that cannot
+ * be stored: FW_ERR_CAPACITY; in each case the whole push is refused and nothing changed. */
+int fw_over_push_batch(fw_over* op, const int64_t* key, const int64_t* rowtime, const int64_t* cols,
+                       const uint8_t* nulls, const int32_t* key_hash, int64_t n);
+int fw_over_push_batch_device(fw_over* op, const int64_t* key, const int64_t* rowtime, const int64_t* cols,
+                              const uint8_t* nulls, const int32_t* key_hash, int64_t n);
+/* onTimer for every registered row time <= wm (RowTimeBoundedRangeOver.scala:140-247, RowTimeBoundedRowsOver.scala
+ * :149-267, RowTimeUnboundedOver.scala:140-211 and :267-335): the rows that fire are appended to the pending output,
+ * a key's rows in (row time, arrival) order; *n_rows (may be NULL) = rows this call emitted.  A watermark lower than
+ * the current one: FW_ERR_ARG. */
+int fw_over_advance_watermark(fw_over* op, int64_t wm, int64_t* n_rows);
+/* copies up to cap pending output rows to host buffers and removes them; epoch[i] (may be NULL) = the number of the
+ * fw_over_advance_watermark call that emitted row i (0-based) */
+int fw_over_drain(fw_over* op, const fw_over_rows* dst, int64_t* epoch, int64_t cap, int64_t* n);
+/* the pending output rows in HBM (valid until the next call on the handle); they stay pending */
+int fw_over_rows_device(fw_over* op, fw_over_rows* rows, int64_t* n);
+/* discards the pending output rows (a sink that read them through fw_over_rows_device) */
+int fw_over_clear_pending(fw_over* op);
+int fw_over_get_stats(fw_over* op, fw_over_stats* out);
+/* snapshotState / initializeState of the keyed state (lastTriggeringTs, the accumulator Row, the MapState of rows).
+ * Snapshot: *n_keys / *n_rows = the key group's totals; the columns are written when dst is non-NULL and both
+ * capacities suffice.  Restore works into any parallelism; refused with nothing changed: key_group outside the
+ * handle's range or a Long / Integer key that is not in key_group (FW_ERR_KEY_GROUP); a key that occurs twice or
+ * already has state (FW_ERR_STATE).  Later pushes are numbered after the largest restored ordinal.  The watermark is
+ * not keyed state: a restored handle starts at Long.MIN_VALUE, as the reference's timer service does, and the host
+ * advances it to the job's watermark again before it pushes on (the unbounded kinds test rows against it). */
+int fw_over_snapshot_key_group(fw_over* op, int32_t key_group, const fw_over_state* dst, int64_t cap_keys,
+                               int64_t cap_rows, int64_t* n_keys, int64_t* n_rows);
+int fw_over_restore_key_group(fw_over* op, int32_t key_group, const fw_over_state* src, int64_t n_keys,
+                              int64_t n_rows);
+
 #ifdef __cplusplus
 }
 #endif
