@@ -6836,46 +6836,6 @@ __global__ void k_reset_regions(DevCfg c, DevTable tb) {
   tb.passes[p] = 0;
 }
 
-// ---- keyed-state snapshot of one key group (HeapKeyedStateBackend.snapshot writes per key group,
-// HeapKeyedStateBackend.java:370-381): one workgroup per partition of the key group; each compacts
-// its region's live entries into the output columns behind one atomic reservation.
-__global__ __launch_bounds__(FW_FIRE_THREADS) void k_snapshot(DevCfg c, DevTable tb, int32_t p0, StateCols out,
-                                                             unsigned long long* count) {
-  __shared__ uint32_t sw[FW_FIRE_THREADS / 64 + 1];
-  __shared__ unsigned long long base_s;
-  const int32_t p = p0 + blockIdx.x;
-  const Region r = region_of(c, tb, p, tb.cur[p]);
-  // (dense regions: the live prefix, no state words)
-  const uint32_t R = c.dense ? (uint32_t)tb.live[p] : r.mask + 1;
-  // one pass per block of the region: count, reserve, write
-  for (uint32_t s0 = 0; s0 < R; s0 += blockDim.x) {
-    const uint32_t s = s0 + threadIdx.x;
-    bool live = s < R && (c.dense || st_kind(ld_state(r.state + s)) == SLOT_LIVE);
-    if (live && c.panes && max(r.ent[s].meta, tb.pane_floor[p]) > jsub(jadd(r.ent[s].start, c.size), 1))
-      live = false;  // a pane whose windows have all been formed (GC'd at the next watermark)
-    uint32_t total;
-    const uint32_t pos = block_excl_scan(live ? 1u : 0u, sw, &total);
-    if (threadIdx.x == 0) base_s = total ? atomicAdd(count, (unsigned long long)total) : 0ull;
-    __syncthreads();
-    if (live) {
-      const Entry e = r.ent[s];
-      const unsigned long long o = base_s + pos;
-      out.key[o] = e.key;
-      out.start[o] = e.start;
-      out.end[o] = e.end;
-      out.cnt[o] = e.cnt;
-      out.sum[o] = sum_out(c, e.sum);
-      out.mn[o] = mn_out(c, e.mn);
-      out.mx[o] = mx_out(c, e.mx);
-      if (agg_by(c.agg)) by_row(c.agg, c.vtype, e, &out.mn[o], &out.mx[o]);
-      // a pane's timer: the maxTimestamp of its next window to form
-      out.timer[o] = c.panes ? max(e.meta, tb.pane_floor[p]) : (e.meta & FW_TIMER) ? 1 : 0;
-      if (out.blk) out.blk[o] = (int64_t)pool_block_of(e);  // exported by k_block_export
-    }
-    __syncthreads();
-  }
-}
-
 // ---- accumulator blocks of the pool aggregates in their snapshot form (flink_window.h, fw_state_block_bytes).
 // One wave per row.  HyperLogLog: the 2^p registers (an unmarked chunk is all zero, so they are copied whole);
 // t-digest: n, then (sum bits, weight) of the live half's centroids, zero-padded.
@@ -7017,9 +6977,245 @@ __global__ void k_restore_count(DevCfg c, int32_t kg, StateCols in, int64_t n, i
     atomicAdd(&demand[p], 1);
 }
 
-// insert (or merge) restored rows; the table has room for all of them (k_restore_count + growth)
-__global__ void k_restore(DevCfg c, int32_t kg, StateCols in, int64_t n, DevTable tb, Status* st,
-                          const int32_t* round_of, int32_t round) {
+// ============================================================== keyed state: snapshot, restore, fw_get_stats
+// One key group's entries as fw_state_rows and back (HeapKeyedStateBackend.snapshot writes per key group,
+// HeapKeyedStateBackend.java:370-381), and the table walk behind numKeyedStateEntries / numEventTimeTimers.  The
+// three kernels are written once.  What the handle's trigger changes is what Entry::meta holds, and TrigState<TRIG>
+// is exactly that:
+//   TRIG_EVENT_TIME  FW_TIMER (maxTimestamp's timer), a pane's next window end, or with the timer a pool block's id;
+//                    dense regions are a live prefix without state words
+//   TRIG_CONTINUOUS  the fire time and its flags (fw_cont.h).  The extra column is the fire time (Long.MIN_VALUE =
+//                    null); the timer column's bit 0 = maxTimestamp's timer, bit 1 = the timer at the fire time
+//   TRIG_COUNT       the trigger's count above FW_CT_SHIFT, which is the extra column; no timer at maxTimestamp
+//                    (CountTrigger.onEventTime is never asked)
+// Under the two triggers an emptied entry is a row too: its trigger state and its timers are state.
+//   slots / is_row   the slots of a region a walk visits, and which of them are rows
+//   snapshot_meta    the timer column and what rides beside the row
+//   restore_entry    row i's accumulator and meta in the table's form, behind the shared columns
+//   merge_meta       row d onto the entry already there; insert_meta: d's meta before it takes a slot (false: refused)
+//   next_timer       the entry's earliest pending timer
+//   stats            an entry's share of {live entries, event-time timers}
+template <int TRIG>
+struct TrigState;
+
+template <>
+struct TrigState<TRIG_EVENT_TIME> {
+  static __device__ __forceinline__ uint32_t slots(const DevCfg& c, const DevTable& tb, int32_t p, const Region& r) {
+    return c.dense ? (uint32_t)tb.live[p] : r.mask + 1;
+  }
+  static __device__ __forceinline__ bool is_row(const DevCfg& c, const DevTable& tb, int32_t p, const Region& r,
+                                                uint32_t s) {
+    if (!c.dense && st_kind(ld_state(r.state + s)) != SLOT_LIVE) return false;
+    // (a pane whose windows have all been formed is garbage, GC'd at the next watermark)
+    return !(c.panes && max(r.ent[s].meta, tb.pane_floor[p]) > jsub(jadd(r.ent[s].start, c.size), 1));
+  }
+  static __device__ __forceinline__ void snapshot_meta(const DevCfg& c, const DevTable& tb, int32_t p, const Entry& e,
+                                                       const StateCols& out, int64_t*, unsigned long long o) {
+    if (agg_by(c.agg)) by_row(c.agg, c.vtype, e, &out.mn[o], &out.mx[o]);
+    // a pane's timer: the maxTimestamp of its next window to form
+    out.timer[o] = c.panes ? max(e.meta, tb.pane_floor[p]) : (e.meta & FW_TIMER) ? 1 : 0;
+    if (out.blk) out.blk[o] = (int64_t)pool_block_of(e);  // exported by k_block_export
+  }
+  static __device__ __forceinline__ void restore_entry(const DevCfg& c, const StateCols& in, const int64_t*, int64_t i,
+                                                       Entry& d) {
+    if (c.agg == FW_AGG_FIRST_MAX) d.mn = ~d.mn;
+    if (agg_first(c.agg)) d.mx = ~in.mx[i];
+    if (agg_by(c.agg)) {  // (the selected field, its ordinal)
+      d.mn = by_key(c.agg, c.vtype, in.mn[i]);
+      d.mx = in.mx[i];
+    }
+    d.meta = c.panes ? in.timer[i] : in.timer[i] ? FW_TIMER : 0;
+  }
+  // register max / the Table aggregates' merge into the entry's block; a digest is not re-compressed here
+  static __device__ __forceinline__ bool merge_meta(const DevCfg& c, const StateCols& in, const int64_t*, int64_t i,
+                                                    Entry& cur, const Entry& d, Status* st) {
+    if (c.pool_bytes) {
+      if (c.agg != FW_AGG_HLL && c.agg != FW_AGG_ROW) {
+        atomicAdd(&st->acc_refused, 1);
+        return false;
+      }
+      block_import(c, pool_block_of(cur), in.acc + i * in.acc_bytes, true);
+    }
+    cur.meta = c.panes ? min(cur.meta, d.meta) : (cur.meta | d.meta);
+    return true;
+  }
+  // a new window of a pool aggregate takes the next block the host set aside
+  static __device__ __forceinline__ bool insert_meta(const DevCfg& c, const StateCols& in, const int64_t*, int64_t i,
+                                                     Entry& d, Status* st) {
+    if (!c.pool_bytes) return true;
+    const uint8_t* acc = in.acc + i * in.acc_bytes;
+    if (!acc_valid(c, acc)) {
+      atomicAdd(&st->acc_refused, 1);
+      return false;
+    }
+    const uint64_t b = (uint64_t)in.blk[atomicAdd(in.used, 1)];
+    block_import(c, b, acc, false);
+    d.meta |= (int64_t)(b << 1);
+    return true;
+  }
+  static __device__ __forceinline__ int64_t next_timer(const DevCfg& c, const Entry& e) { return entry_timer(c, e); }
+  static __device__ __forceinline__ void stats(const DevCfg& c, const Entry& e, unsigned long long* live,
+                                               unsigned long long* timers) {
+    *live += 1;
+    if (c.panes) {  // one pending timer per pane (its next window end)
+      *timers += 1;
+      return;
+    }
+    const int64_t mx = jsub(e.end, 1), cl = cleanup_of(e.end, c.lateness);
+    if (e.meta & FW_TIMER) *timers += 1;
+    if (cl != LMAX && !((e.meta & FW_TIMER) && cl == mx)) *timers += 1;
+  }
+};
+
+// the two triggers' tables: every SLOT_LIVE entry, the emptied ones included
+struct TrigSlots {
+  static __device__ __forceinline__ uint32_t slots(const DevCfg&, const DevTable&, int32_t, const Region& r) {
+    return r.mask + 1;
+  }
+  static __device__ __forceinline__ bool is_row(const DevCfg&, const DevTable&, int32_t, const Region& r, uint32_t s) {
+    return st_kind(ld_state(r.state + s)) == SLOT_LIVE;
+  }
+};
+
+template <>
+struct TrigState<TRIG_CONTINUOUS> : TrigSlots {
+  static __device__ __forceinline__ void snapshot_meta(const DevCfg&, const DevTable&, int32_t, const Entry& e,
+                                                       const StateCols& out, int64_t* fire, unsigned long long o) {
+    out.timer[o] = e.meta & (FW_CF_MTIMER | FW_CF_REG);
+    fire[o] = (e.meta & FW_CF_SET) ? fw_cf_fire(e.meta, e.start) : LMIN;
+  }
+  static __device__ __forceinline__ void restore_entry(const DevCfg& c, const StateCols&, const int64_t*, int64_t,
+                                                       Entry& d) {
+    if (d.cnt == 0) acc_clear(c, d);
+  }
+  // row i's fire time and flags (null: no timer behind it)
+  static __device__ __forceinline__ void row_fire(const StateCols& in, const int64_t* fire, int64_t i, int64_t start,
+                                                  int64_t* df, uint32_t* dfl) {
+    *df = fire[i];
+    *dfl = (uint32_t)in.timer[i] & (FW_CF_MTIMER | FW_CF_REG);
+    if (*df != LMIN) {
+      *dfl |= FW_CF_SET;
+    } else {
+      *dfl &= ~FW_CF_REG;
+      *df = start;
+    }
+  }
+  // the fire time by Min as the trigger's ReducingState does, the timers of the surviving fire time
+  static __device__ __forceinline__ bool merge_meta(const DevCfg&, const StateCols& in, const int64_t* fire, int64_t i,
+                                                    Entry& cur, const Entry& d, Status* st) {
+    int64_t df;
+    uint32_t dfl;
+    row_fire(in, fire, i, d.start, &df, &dfl);
+    int64_t cf = fw_cf_fire(cur.meta, cur.start);
+    uint32_t cfl = fw_cf_flags(cur.meta);
+    const uint32_t mt = (cfl | dfl) & FW_CF_MTIMER;
+    if ((dfl & FW_CF_SET) && (!(cfl & FW_CF_SET) || df < cf)) {
+      cf = df;
+      cfl = dfl;
+    } else if ((dfl & FW_CF_SET) && df == cf) {
+      cfl |= dfl;
+    }
+    cfl = (cfl & ~FW_CF_MTIMER) | mt;
+    if (!fw_cf_pack(cur.start, cf, cfl, &cur.meta)) atomicOr(&st->flags, FW_STATUS_CF_WRAP);
+    return true;
+  }
+  static __device__ __forceinline__ bool insert_meta(const DevCfg&, const StateCols& in, const int64_t* fire, int64_t i,
+                                                     Entry& d, Status* st) {
+    int64_t df;
+    uint32_t dfl;
+    row_fire(in, fire, i, d.start, &df, &dfl);
+    if (!fw_cf_pack(d.start, df, dfl, &d.meta)) atomicOr(&st->flags, FW_STATUS_CF_WRAP);
+    return true;
+  }
+  static __device__ __forceinline__ int64_t next_timer(const DevCfg& c, const Entry& e) {
+    return fw_cf_next(jsub(e.end, 1), cleanup_of(e.end, c.lateness), fw_cf_fire(e.meta, e.start), fw_cf_flags(e.meta));
+  }
+  // entries with contents; maxTimestamp, fire time and cleanup time of every entry, coinciding times once
+  // (HeapInternalTimerService keeps a set)
+  static __device__ __forceinline__ void stats(const DevCfg& c, const Entry& e, unsigned long long* live,
+                                               unsigned long long* timers) {
+    const int64_t meta = e.meta, C = cleanup_of(e.end, c.lateness);
+    *live += e.cnt > 0;
+    *timers += (unsigned)fw_cf_timers(jsub(e.end, 1), C, fw_cf_fire(meta, e.start), fw_cf_flags(meta), C != LMAX);
+  }
+};
+
+template <>
+struct TrigState<TRIG_COUNT> : TrigSlots {
+  static __device__ __forceinline__ void snapshot_meta(const DevCfg&, const DevTable&, int32_t, const Entry& e,
+                                                       const StateCols& out, int64_t* tcount, unsigned long long o) {
+    out.timer[o] = 0;
+    tcount[o] = e.meta >> FW_CT_SHIFT;
+  }
+  static __device__ __forceinline__ void restore_entry(const DevCfg& c, const StateCols&, const int64_t* tcount,
+                                                       int64_t i, Entry& d) {
+    if (d.cnt == 0) acc_clear(c, d);
+    d.meta = tcount[i] << FW_CT_SHIFT;
+  }
+  // the counts add without firing (CountTrigger.onMerge / the count's ReducingState, Sum)
+  static __device__ __forceinline__ bool merge_meta(const DevCfg&, const StateCols&, const int64_t*, int64_t,
+                                                    Entry& cur, const Entry& d, Status*) {
+    cur.meta += d.meta;
+    return true;
+  }
+  static __device__ __forceinline__ bool insert_meta(const DevCfg&, const StateCols&, const int64_t*, int64_t, Entry&,
+                                                     Status*) {
+    return true;
+  }
+  static __device__ __forceinline__ int64_t next_timer(const DevCfg& c, const Entry& e) {
+    return cleanup_of(e.end, c.lateness);
+  }
+  // the windows with contents; one cleanup timer per window in flight, the emptied ones included (a cleanup time of
+  // Long.MAX_VALUE registers none, WindowOperator.java:611-617)
+  static __device__ __forceinline__ void stats(const DevCfg& c, const Entry& e, unsigned long long* live,
+                                               unsigned long long* timers) {
+    *live += e.cnt > 0;
+    *timers += cleanup_of(e.end, c.lateness) != LMAX;
+  }
+};
+
+// snapshot of one key group: one workgroup per partition of the key group; each compacts its region's rows into the
+// output columns behind one atomic reservation
+template <int TRIG>
+__global__ __launch_bounds__(FW_FIRE_THREADS) void k_snapshot(DevCfg c, DevTable tb, int32_t p0, StateCols out,
+                                                             int64_t* __restrict__ extra, unsigned long long* count) {
+  using T = TrigState<TRIG>;
+  __shared__ uint32_t sw[FW_FIRE_THREADS / 64 + 1];
+  __shared__ unsigned long long base_s;
+  const int32_t p = p0 + blockIdx.x;
+  const Region r = region_of(c, tb, p, tb.cur[p]);
+  const uint32_t R = T::slots(c, tb, p, r);
+  // one pass per block of the region: count, reserve, write
+  for (uint32_t s0 = 0; s0 < R; s0 += blockDim.x) {
+    const uint32_t s = s0 + threadIdx.x;
+    const bool live = s < R && T::is_row(c, tb, p, r, s);
+    uint32_t total;
+    const uint32_t pos = block_excl_scan(live ? 1u : 0u, sw, &total);
+    if (threadIdx.x == 0) base_s = total ? atomicAdd(count, (unsigned long long)total) : 0ull;
+    __syncthreads();
+    if (live) {
+      const Entry e = r.ent[s];
+      const unsigned long long o = base_s + pos;
+      out.key[o] = e.key;
+      out.start[o] = e.start;
+      out.end[o] = e.end;
+      out.cnt[o] = e.cnt;
+      out.sum[o] = sum_out(c, e.sum);
+      out.mn[o] = mn_out(c, e.mn);
+      out.mx[o] = mx_out(c, e.mx);
+      T::snapshot_meta(c, tb, p, e, out, extra, o);
+    }
+    __syncthreads();
+  }
+}
+
+// insert (or merge) restored rows; the table has room for all of them (k_restore_count + growth).  A row whose
+// (key, window) is already present (restored earlier, or by an earlier round of this call) merges: the accumulators
+// by AggregateFunction.merge, the metas by the trigger's rule
+template <int TRIG>
+__global__ void k_restore(DevCfg c, int32_t kg, StateCols in, const int64_t* __restrict__ extra, int64_t n, DevTable tb,
+                          Status* st, const int32_t* round_of, int32_t round) {
+  using T = TrigState<TRIG>;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || (round_of && round_of[i] != round)) return;
   const int32_t p = restore_partition(c, kg, in.key[i]);
@@ -7031,42 +7227,21 @@ __global__ void k_restore(DevCfg c, int32_t kg, StateCols in, int64_t n, DevTabl
   d.cnt = in.cnt[i];
   d.sum = in.sum[i];
   d.mn = c.vtype == FW_VAL_F64 ? f64_sortable(in.mn[i]) : in.mn[i];
-  if (c.agg == FW_AGG_FIRST_MAX) d.mn = ~d.mn;
-  d.mx = agg_first(c.agg) ? ~in.mx[i] : c.vtype == FW_VAL_F64 ? f64_sortable(in.mx[i]) : in.mx[i];
-  if (agg_by(c.agg)) {  // (the selected field, its ordinal)
-    d.mn = by_key(c.agg, c.vtype, in.mn[i]);
-    d.mx = in.mx[i];
-  }
-  d.meta = c.panes ? in.timer[i] : in.timer[i] ? FW_TIMER : 0;
+  d.mx = c.vtype == FW_VAL_F64 ? f64_sortable(in.mx[i]) : in.mx[i];
+  T::restore_entry(c, in, extra, i, d);
   const Region r = region_of(c, tb, p, tb.cur[p]);
-  const uint64_t h = slot_hash(c, d.key, c.assigner == FW_SESSION ? 0 : d.start);
+  const uint64_t h = slot_hash(c, d.key, TRIG == TRIG_EVENT_TIME && c.assigner == FW_SESSION ? 0 : d.start);
   const int32_t found = region_find(r, h, d.key, d.start, d.end);
-  const uint8_t* acc = in.acc ? in.acc + i * in.acc_bytes : nullptr;
-  if (found >= 0) {  // the window is already there (restored earlier, or an earlier round): AggregateFunction.merge
-    Entry& x = r.ent[found];
-    Entry cur = x;
-    if (c.pool_bytes) {  // register max / the Table aggregates' merge into its block; a digest is not re-compressed here
-      if (c.agg != FW_AGG_HLL && c.agg != FW_AGG_ROW) {
-        atomicAdd(&st->acc_refused, 1);
-        return;
-      }
-      block_import(c, pool_block_of(cur), acc, true);
-    }
+  if (found >= 0) {
+    Entry cur = r.ent[found];
     acc_merge(c, cur, d);
-    cur.meta = c.panes ? min(cur.meta, d.meta) : (cur.meta | d.meta);
-    x = cur;
-    atomicMin((long long*)&tb.next_timer[p], (long long)entry_timer(c, cur));
+    if (!T::merge_meta(c, in, extra, i, cur, d, st)) return;
+    r.ent[found] = cur;
+    // (added counts move no timer: the window's cleanup time is in next_timer since it was inserted)
+    if constexpr (TRIG != TRIG_COUNT) atomicMin((long long*)&tb.next_timer[p], (long long)T::next_timer(c, cur));
     return;
   }
-  if (c.pool_bytes) {
-    if (!acc_valid(c, acc)) {
-      atomicAdd(&st->acc_refused, 1);
-      return;
-    }
-    const uint64_t b = (uint64_t)in.blk[atomicAdd(in.used, 1)];
-    block_import(c, b, acc, false);
-    d.meta |= (int64_t)(b << 1);
-  }
+  if (!T::insert_meta(c, in, extra, i, d, st)) return;
   const int32_t s = region_claim(r, h, SLOT_BUSY);
   if (s < 0) {
     atomicOr(&st->flags, FW_STATUS_STATE_LOST);
@@ -7076,9 +7251,22 @@ __global__ void k_restore(DevCfg c, int32_t kg, StateCols in, int64_t n, DevTabl
   __threadfence();
   __hip_atomic_store(r.state + s, live_word(h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   atomicAdd(&tb.live[p], 1);
-  atomicMin((long long*)&tb.next_timer[p], (long long)entry_timer(c, d));
+  atomicMin((long long*)&tb.next_timer[p], (long long)T::next_timer(c, d));
 }
 
+// out3 = {live entries, event-time timers}
+template <int TRIG>
+__global__ __launch_bounds__(FW_FIRE_THREADS) void k_table_stats(DevCfg c, DevTable tb, unsigned long long* out3) {
+  using T = TrigState<TRIG>;
+  const int32_t p = blockIdx.x;
+  const Region r = region_of(c, tb, p, tb.cur[p]);
+  unsigned long long live = 0, timers = 0;
+  const uint32_t R = T::slots(c, tb, p, r);
+  for (uint32_t s = threadIdx.x; s < R; s += blockDim.x)
+    if (T::is_row(c, tb, p, r, s)) T::stats(c, r.ent[s], &live, &timers);
+  if (live) atomicAdd(&out3[0], live);
+  if (timers) atomicAdd(&out3[1], timers);
+}
 
 // ============================================================== pre-shuffle combining
 // A combiner operator (full KeyGroupRange, watermark never advanced) aggregates a subtask's batch before the keyBy
@@ -7419,30 +7607,6 @@ __global__ __launch_bounds__(256) void k_hll_push_regs(DevCfg c, int64_t wm, Par
     const uint64_t s0 = (uint64_t)__shfl((long long)b0, src, 64), s1 = (uint64_t)__shfl((long long)b1, src, 64);
     for (uint64_t k = s0 + lane; k < s1; k += 64) hll_raise_jr(c, b, regs[k] >> 8, regs[k] & 0xffu);
   }
-}
-
-// out3 = {live entries, event-time timers}
-__global__ __launch_bounds__(FW_FIRE_THREADS) void k_table_stats(DevCfg c, DevTable tb, unsigned long long* out3) {
-  const int32_t p = blockIdx.x;
-  const Region r = region_of(c, tb, p, tb.cur[p]);
-  unsigned long long live = 0, timers = 0;
-  const uint32_t lim = c.dense ? (uint32_t)tb.live[p] : r.mask + 1;  // (dense regions: the live prefix)
-  for (uint32_t s = threadIdx.x; s < lim; s += blockDim.x) {
-    if (!c.dense && st_kind(ld_state(r.state + s)) != SLOT_LIVE) continue;
-    const Entry& e = r.ent[s];
-    if (c.panes) {  // one pending timer per pane (its next window end); formed-out panes are garbage
-      if (max(e.meta, tb.pane_floor[p]) > jsub(jadd(e.start, c.size), 1)) continue;
-      live++;
-      timers++;
-      continue;
-    }
-    live++;
-    const int64_t mx = jsub(e.end, 1), cl = cleanup_of(e.end, c.lateness);
-    if (e.meta & FW_TIMER) timers++;
-    if (cl != LMAX && !((e.meta & FW_TIMER) && cl == mx)) timers++;
-  }
-  if (live) atomicAdd(&out3[0], live);
-  if (timers) atomicAdd(&out3[1], timers);
 }
 
 // ============================================================== dense tumbling regions (DevCfg::dense)
@@ -8917,117 +9081,6 @@ __global__ __launch_bounds__(FW_FIRE_THREADS) void k_cf_fire(DevCfg c, int64_t w
   }
 }
 
-// numKeyedStateEntries / numEventTimeTimers: entries with contents; maxTimestamp, fire time and cleanup time of every
-// entry, coinciding times once (HeapInternalTimerService keeps a set)
-__global__ __launch_bounds__(FW_FIRE_THREADS) void k_cf_stats(DevCfg c, DevTable tb, unsigned long long* out3) {
-  const int32_t p = blockIdx.x;
-  const Region r = region_of(c, tb, p, tb.cur[p]);
-  unsigned long long live = 0, timers = 0;
-  for (uint32_t s = threadIdx.x; s <= r.mask; s += blockDim.x) {
-    if (st_kind(ld_state(r.state + s)) != SLOT_LIVE) continue;
-    const Entry& e = r.ent[s];
-    const int64_t meta = e.meta, C = cleanup_of(e.end, c.lateness);
-    live += e.cnt > 0;
-    timers += (unsigned)fw_cf_timers(jsub(e.end, 1), C, fw_cf_fire(meta, e.start), fw_cf_flags(meta), C != LMAX);
-  }
-  if (live) atomicAdd(&out3[0], live);
-  if (timers) atomicAdd(&out3[1], timers);
-}
-
-// keyed-state snapshot with the trigger state (k_snapshot's rows plus the fire time; an emptied entry is a row too:
-// its fire time and timers are state)
-__global__ __launch_bounds__(FW_FIRE_THREADS) void k_cf_snapshot(DevCfg c, DevTable tb, int32_t p0, StateCols out,
-                                                                int64_t* __restrict__ fire, unsigned long long* count) {
-  __shared__ uint32_t sw[FW_FIRE_THREADS / 64 + 1];
-  __shared__ unsigned long long base_s;
-  const int32_t p = p0 + blockIdx.x;
-  const Region r = region_of(c, tb, p, tb.cur[p]);
-  const uint32_t R = r.mask + 1;
-  for (uint32_t s0 = 0; s0 < R; s0 += blockDim.x) {
-    const uint32_t s = s0 + threadIdx.x;
-    const bool live = s < R && st_kind(ld_state(r.state + s)) == SLOT_LIVE;
-    uint32_t total;
-    const uint32_t pos = block_excl_scan(live ? 1u : 0u, sw, &total);
-    if (threadIdx.x == 0) base_s = total ? atomicAdd(count, (unsigned long long)total) : 0ull;
-    __syncthreads();
-    if (live) {
-      const Entry e = r.ent[s];
-      const unsigned long long o = base_s + pos;
-      out.key[o] = e.key;
-      out.start[o] = e.start;
-      out.end[o] = e.end;
-      out.cnt[o] = e.cnt;
-      out.sum[o] = sum_out(c, e.sum);
-      out.mn[o] = mn_out(c, e.mn);
-      out.mx[o] = mx_out(c, e.mx);
-      out.timer[o] = e.meta & (FW_CF_MTIMER | FW_CF_REG);
-      fire[o] = (e.meta & FW_CF_SET) ? fw_cf_fire(e.meta, e.start) : LMIN;
-    }
-    __syncthreads();
-  }
-}
-
-// restore of such rows (k_restore with the trigger state).  A row whose (key, window) is already present merges:
-// the accumulators by AggregateFunction.merge, the fire time by Min as the trigger's ReducingState does, the timers
-// of the surviving fire time
-__global__ void k_cf_restore(DevCfg c, int32_t kg, StateCols in, const int64_t* __restrict__ fire, int64_t n,
-                             DevTable tb, Status* st, const int32_t* round_of, int32_t round) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || (round_of && round_of[i] != round)) return;
-  const int32_t p = restore_partition(c, kg, in.key[i]);
-  if (p < 0) return;
-  Entry d;
-  d.key = in.key[i];
-  d.start = in.start[i];
-  d.end = in.end[i];
-  d.cnt = in.cnt[i];
-  d.sum = in.sum[i];
-  d.mn = c.vtype == FW_VAL_F64 ? f64_sortable(in.mn[i]) : in.mn[i];
-  d.mx = c.vtype == FW_VAL_F64 ? f64_sortable(in.mx[i]) : in.mx[i];
-  if (d.cnt == 0) acc_clear(c, d);
-  int64_t df = fire[i];
-  uint32_t dfl = (uint32_t)in.timer[i] & (FW_CF_MTIMER | FW_CF_REG);
-  if (df != LMIN) {
-    dfl |= FW_CF_SET;
-  } else {  // null: no timer behind it
-    dfl &= ~FW_CF_REG;
-    df = d.start;
-  }
-  const int64_t M = jsub(d.end, 1), C = cleanup_of(d.end, c.lateness);
-  const Region r = region_of(c, tb, p, tb.cur[p]);
-  const uint64_t h = slot_hash(c, d.key, d.start);
-  const int32_t found = region_find(r, h, d.key, d.start, d.end);
-  if (found >= 0) {
-    Entry cur = r.ent[found];
-    acc_merge(c, cur, d);
-    int64_t cf = fw_cf_fire(cur.meta, cur.start);
-    uint32_t cfl = fw_cf_flags(cur.meta);
-    const uint32_t mt = (cfl | dfl) & FW_CF_MTIMER;
-    if ((dfl & FW_CF_SET) && (!(cfl & FW_CF_SET) || df < cf)) {
-      cf = df;
-      cfl = dfl;
-    } else if ((dfl & FW_CF_SET) && df == cf) {
-      cfl |= dfl;
-    }
-    cfl = (cfl & ~FW_CF_MTIMER) | mt;
-    if (!fw_cf_pack(cur.start, cf, cfl, &cur.meta)) atomicOr(&st->flags, FW_STATUS_CF_WRAP);
-    r.ent[found] = cur;
-    atomicMin((long long*)&tb.next_timer[p], (long long)fw_cf_next(M, C, cf, cfl));
-    return;
-  }
-  if (!fw_cf_pack(d.start, df, dfl, &d.meta)) atomicOr(&st->flags, FW_STATUS_CF_WRAP);
-  const int32_t s = region_claim(r, h, SLOT_BUSY);
-  if (s < 0) {
-    atomicOr(&st->flags, FW_STATUS_STATE_LOST);
-    return;
-  }
-  r.ent[s] = d;
-  __threadfence();
-  __hip_atomic_store(r.state + s, live_word(h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  atomicAdd(&tb.live[p], 1);
-  atomicMin((long long*)&tb.next_timer[p], (long long)fw_cf_next(M, C, df, dfl));
-}
-
 // ============================================================== CountTrigger over time windows (fw_create_count_trigger)
 // .trigger(CountTrigger.of(n)) on the aggregating operator, optionally inside PurgingTrigger (CountTrigger.java:47-85
 // under WindowOperator.processElement, WindowOperator.java:379-407).  Per element and window that is not late: add,
@@ -9405,93 +9458,6 @@ __global__ __launch_bounds__(256) void k_ct_fold(DevCfg c, const uint32_t* __res
     tb.ent[cur][g] = tb.ent[cur ^ 1][g];
   }
 }
-// numKeyedStateEntries: the windows with contents; numEventTimeTimers: one cleanup timer per window in flight, the
-// emptied ones included (a cleanup time of Long.MAX_VALUE registers none, WindowOperator.java:611-617)
-__global__ __launch_bounds__(FW_FIRE_THREADS) void k_ct_stats(DevCfg c, DevTable tb, unsigned long long* out3) {
-  const int32_t p = blockIdx.x;
-  const Region r = region_of(c, tb, p, tb.cur[p]);
-  unsigned long long live = 0, timers = 0;
-  for (uint32_t s = threadIdx.x; s <= r.mask; s += blockDim.x) {
-    if (st_kind(ld_state(r.state + s)) != SLOT_LIVE) continue;
-    const Entry& e = r.ent[s];
-    live += e.cnt > 0;
-    timers += cleanup_of(e.end, c.lateness) != LMAX;
-  }
-  if (live) atomicAdd(&out3[0], live);
-  if (timers) atomicAdd(&out3[1], timers);
-}
-// keyed-state snapshot with the trigger's count (k_snapshot's rows; an emptied window is a row too: its count and its
-// cleanup timer are state)
-__global__ __launch_bounds__(FW_FIRE_THREADS) void k_ct_snapshot(DevCfg c, DevTable tb, int32_t p0, StateCols out,
-                                                                int64_t* __restrict__ tcount, unsigned long long* count) {
-  __shared__ uint32_t sw[FW_FIRE_THREADS / 64 + 1];
-  __shared__ unsigned long long base_s;
-  const int32_t p = p0 + blockIdx.x;
-  const Region r = region_of(c, tb, p, tb.cur[p]);
-  const uint32_t R = r.mask + 1;
-  for (uint32_t s0 = 0; s0 < R; s0 += blockDim.x) {
-    const uint32_t s = s0 + threadIdx.x;
-    const bool live = s < R && st_kind(ld_state(r.state + s)) == SLOT_LIVE;
-    uint32_t total;
-    const uint32_t pos = block_excl_scan(live ? 1u : 0u, sw, &total);
-    if (threadIdx.x == 0) base_s = total ? atomicAdd(count, (unsigned long long)total) : 0ull;
-    __syncthreads();
-    if (live) {
-      const Entry e = r.ent[s];
-      const unsigned long long o = base_s + pos;
-      out.key[o] = e.key;
-      out.start[o] = e.start;
-      out.end[o] = e.end;
-      out.cnt[o] = e.cnt;
-      out.sum[o] = sum_out(c, e.sum);
-      out.mn[o] = mn_out(c, e.mn);
-      out.mx[o] = mx_out(c, e.mx);
-      out.timer[o] = 0;  // (no timer at maxTimestamp: CountTrigger.onEventTime is never asked)
-      tcount[o] = e.meta >> FW_CT_SHIFT;
-    }
-    __syncthreads();
-  }
-}
-// restore of such rows; a row whose (key, window) is present merges, the counts add without firing
-// (CountTrigger.onMerge / the count's ReducingState, Sum)
-__global__ void k_ct_restore(DevCfg c, int32_t kg, StateCols in, const int64_t* __restrict__ tcount, int64_t n,
-                             DevTable tb, Status* st, const int32_t* round_of, int32_t round) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || (round_of && round_of[i] != round)) return;
-  const int32_t p = restore_partition(c, kg, in.key[i]);
-  if (p < 0) return;
-  Entry d;
-  d.key = in.key[i];
-  d.start = in.start[i];
-  d.end = in.end[i];
-  d.cnt = in.cnt[i];
-  d.sum = in.sum[i];
-  d.mn = c.vtype == FW_VAL_F64 ? f64_sortable(in.mn[i]) : in.mn[i];
-  d.mx = c.vtype == FW_VAL_F64 ? f64_sortable(in.mx[i]) : in.mx[i];
-  if (d.cnt == 0) acc_clear(c, d);
-  d.meta = tcount[i] << FW_CT_SHIFT;
-  const Region r = region_of(c, tb, p, tb.cur[p]);
-  const uint64_t h = slot_hash(c, d.key, d.start);
-  const int32_t found = region_find(r, h, d.key, d.start, d.end);
-  if (found >= 0) {
-    Entry cur = r.ent[found];
-    acc_merge(c, cur, d);
-    cur.meta += d.meta;
-    r.ent[found] = cur;
-    return;
-  }
-  const int32_t s = region_claim(r, h, SLOT_BUSY);
-  if (s < 0) {
-    atomicOr(&st->flags, FW_STATUS_STATE_LOST);
-    return;
-  }
-  r.ent[s] = d;
-  __threadfence();
-  __hip_atomic_store(r.state + s, live_word(h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  atomicAdd(&tb.live[p], 1);
-  atomicMin((long long*)&tb.next_timer[p], (long long)cleanup_of(d.end, c.lateness));
-}
-
 }  // namespace
 
 // ============================================================================== launchers
@@ -9784,19 +9750,6 @@ void launch_cont_count(const DevCfg& c, int64_t wm, DevTable tb, unsigned long l
 void launch_cont_fire(const DevCfg& c, int64_t wm, DevTable tb, DevRows out, Status* st, hipStream_t s) {
   FW_LAUNCH_MAIN(k_cf_fire, dim3(c.P), dim3(FW_FIRE_THREADS), 0, s, c, wm, tb, out, st);
 }
-void launch_cont_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t s) {
-  hipLaunchKernelGGL(k_cf_stats, dim3(c.P), dim3(FW_FIRE_THREADS), 0, s, c, tb, out3);
-}
-void launch_cont_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, StateCols out, int64_t* fire,
-                          unsigned long long* count, hipStream_t s) {
-  hipLaunchKernelGGL(k_cf_snapshot, dim3(np), dim3(FW_FIRE_THREADS), 0, s, c, tb, p0, out, fire, count);
-}
-void launch_cont_restore(const DevCfg& c, int32_t kg, StateCols in, const int64_t* fire, int64_t n, DevTable tb,
-                         Status* st, const int32_t* round_of, int32_t rounds, hipStream_t s) {
-  const dim3 grid((unsigned)((n + 255) / 256));
-  for (int32_t r = 0; r < rounds; r++)
-    hipLaunchKernelGGL(k_cf_restore, grid, dim3(256), 0, s, c, kg, in, fire, n, tb, st, round_of, r);
-}
 
 // ---- CountTrigger over time windows
 size_t ct_sort_bytes(int64_t n) {
@@ -9847,19 +9800,6 @@ void launch_ct_fire(const DevCfg& c, const int64_t* val, int64_t items, const Ct
   FW_LAUNCH_MAIN(k_ct_scan<true>, dim3((unsigned)nt), dim3(FW_CT_THREADS), 0, s, c, b.nfire, sk, sv, val,
                  (const uint32_t*)b.first, items, tb, b.tile, out, st);
   hipLaunchKernelGGL(k_ct_fold, dim3(ct_grid(items)), dim3(256), 0, s, c, sk, items, tb);
-}
-void launch_ct_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t s) {
-  hipLaunchKernelGGL(k_ct_stats, dim3(c.P), dim3(FW_FIRE_THREADS), 0, s, c, tb, out3);
-}
-void launch_ct_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, StateCols out, int64_t* tcount,
-                        unsigned long long* count, hipStream_t s) {
-  hipLaunchKernelGGL(k_ct_snapshot, dim3(np), dim3(FW_FIRE_THREADS), 0, s, c, tb, p0, out, tcount, count);
-}
-void launch_ct_restore(const DevCfg& c, int32_t kg, StateCols in, const int64_t* tcount, int64_t n, DevTable tb,
-                       Status* st, const int32_t* round_of, int32_t rounds, hipStream_t s) {
-  const dim3 grid((unsigned)((n + 255) / 256));
-  for (int32_t r = 0; r < rounds; r++)
-    hipLaunchKernelGGL(k_ct_restore, grid, dim3(256), 0, s, c, kg, in, tcount, n, tb, st, round_of, r);
 }
 
 void launch_fire(const DevCfg& c0, int64_t wm, DevTable tb, DevRows out, Status* st, hipStream_t s) {
@@ -10040,10 +9980,19 @@ void launch_rehash(const DevCfg& oc, DevTable ot, const DevCfg& nc, DevTable nt,
     hipLaunchKernelGGL(k_rehash, dim3(oc.P), dim3(FW_FIRE_THREADS), 0, s, oc, ot, nc, nt);
 }
 
-
-void launch_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, StateCols out, unsigned long long* count,
-                     hipStream_t s) {
-  hipLaunchKernelGGL(k_snapshot, dim3(np), dim3(FW_FIRE_THREADS), 0, s, c, tb, p0, out, count);
+// the keyed-state kernels' instantiation for a handle's trigger
+#define FW_LAUNCH_TRIG(trig, kern, grid, block, s, ...)                                                    \
+  switch (trig) {                                                                                          \
+    case TRIG_EVENT_TIME: hipLaunchKernelGGL(kern<TRIG_EVENT_TIME>, grid, block, 0, s, __VA_ARGS__); break; \
+    case TRIG_CONTINUOUS: hipLaunchKernelGGL(kern<TRIG_CONTINUOUS>, grid, block, 0, s, __VA_ARGS__); break; \
+    case TRIG_COUNT: hipLaunchKernelGGL(kern<TRIG_COUNT>, grid, block, 0, s, __VA_ARGS__); break;          \
+  }
+void launch_snapshot(const DevCfg& c, TrigKind trig, DevTable tb, int32_t p0, int32_t np, StateCols out, int64_t* extra,
+                     unsigned long long* count, hipStream_t s) {
+  FW_LAUNCH_TRIG(trig, k_snapshot, dim3(np), dim3(FW_FIRE_THREADS), s, c, tb, p0, out, extra, count);
+}
+void launch_table_stats(const DevCfg& c, TrigKind trig, DevTable tb, unsigned long long* out3, hipStream_t s) {
+  FW_LAUNCH_TRIG(trig, k_table_stats, dim3(c.P), dim3(FW_FIRE_THREADS), s, c, tb, out3);
 }
 void launch_block_export(const DevCfg& c, const int64_t* blk, int64_t n, uint8_t* acc, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_block_export, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, c, blk, n, acc);
@@ -10054,18 +10003,19 @@ void launch_pool_take(const DevCfg& c, int32_t h, int32_t take, int64_t bump, in
 void launch_pool_give(const DevCfg& c, const int64_t* ids, int64_t n, int32_t h, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_pool_give, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c, ids, n, h);
 }
-void launch_restore(const DevCfg& c, int32_t kg, StateCols in, int64_t n, int32_t* demand, DevTable tb, Status* st,
-                    const int32_t* round_of, int32_t rounds, hipStream_t s) {
+void launch_restore_count(const DevCfg& c, int32_t kg, StateCols in, int64_t n, int32_t* demand, Status* st,
+                          hipStream_t s) {
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  if (!blocks) return;
-  if (demand) {
-    hipLaunchKernelGGL(k_restore_count, dim3(blocks), dim3(256), 0, s, c, kg, in, n, demand, st);
-    return;
-  }
+  if (blocks) hipLaunchKernelGGL(k_restore_count, dim3(blocks), dim3(256), 0, s, c, kg, in, n, demand, st);
+}
+void launch_restore(const DevCfg& c, TrigKind trig, int32_t kg, StateCols in, const int64_t* extra, int64_t n,
+                    DevTable tb, Status* st, const int32_t* round_of, int32_t rounds, hipStream_t s) {
+  const dim3 blocks((unsigned)((n + 255) / 256));
+  if (!blocks.x) return;
   // rows restoring the same (key, window) twice go in different rounds, so each round inserts a window at
   // most once and later rounds merge into it (one launch per round, stream-ordered)
   for (int32_t r = 0; r < std::max(1, rounds); r++)
-    hipLaunchKernelGGL(k_restore, dim3(blocks), dim3(256), 0, s, c, kg, in, n, tb, st, round_of, r);
+    FW_LAUNCH_TRIG(trig, k_restore, blocks, dim3(256), s, c, kg, in, extra, n, tb, st, round_of, r);
 }
 
 void launch_live_offsets(const DevCfg& c, DevTable tb, uint32_t* offs, uint32_t* scratch, hipStream_t s) {
@@ -10123,9 +10073,6 @@ void launch_dt_restore_runs(const DevCfg& c, int32_t kg, StateCols in, int64_t n
   launch_scan(hist, (int64_t)(c.P + 1) * T, scan_tmp, s);
   hipLaunchKernelGGL(k_dt_rows_scatter, dim3(T), dim3(FW_TILE_THREADS), (size_t)c.P * sizeof(uint32_t), s, c.P,
                      (const int32_t*)rp, (const PartialRec*)tmp, n, T, (const uint32_t*)hist, part);
-}
-void launch_table_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t s) {
-  hipLaunchKernelGGL(k_table_stats, dim3(c.P), dim3(FW_FIRE_THREADS), 0, s, c, tb, out3);
 }
 
 void launch_reset_regions(const DevCfg& c, DevTable tb, hipStream_t s) {

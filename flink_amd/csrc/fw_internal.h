@@ -212,6 +212,9 @@ struct DevCfg {
 // runs EventTimeTrigger.  Such a handle keeps windows (no panes, dense regions, compact records or single pass) and
 // runs the _cont instantiations and the k_ca / k_cf_* kernels.
 __host__ __device__ inline int64_t cont_iv(const DevCfg& c) { return c.assigner == 2 /* FW_SESSION */ ? 0 : c.gap; }
+// the trigger whose state an entry's meta word carries: what the keyed-state kernels (snapshot, restore, stats) are
+// instantiated by (fw_device.hip TrigState; fw_runtime.cpp trig_kind)
+enum TrigKind { TRIG_EVENT_TIME, TRIG_CONTINUOUS, TRIG_COUNT };
 // FW_AGG_ROW accumulator of one column (40 bytes, zero = empty): the non-null count, the sum (integral columns: 128
 // bits, two's complement, lo / hi; floating columns: f64 in lo), min / max as order keys encoded so that 0 is the
 // identity of an unsigned max (row_enc_min / row_enc_max)
@@ -558,13 +561,6 @@ void launch_cont_arm(const DevCfg& c, int64_t wm, const int64_t* key, const int6
 void launch_cont_count(const DevCfg& c, int64_t wm, DevTable tb, unsigned long long* ctr, hipStream_t_ s);
 // writing pass: the rows, the entries' trigger state, purge / cleanup, survivors into the other buffer, next_timer
 void launch_cont_fire(const DevCfg& c, int64_t wm, DevTable tb, DevRows out, Status* st, hipStream_t_ s);
-void launch_cont_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t_ s);
-// snapshot / restore with the trigger state: fire = the fire time per row (Long.MIN_VALUE = null), the timer column's
-// bit 0 = maxTimestamp's timer, bit 1 = the timer at the fire time
-void launch_cont_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, StateCols out, int64_t* fire,
-                          unsigned long long* count, hipStream_t_ s);
-void launch_cont_restore(const DevCfg& c, int32_t kg, StateCols in, const int64_t* fire, int64_t n, DevTable tb,
-                         Status* st, const int32_t* round_of, int32_t rounds, hipStream_t_ s);
 // ---- CountTrigger over time windows (fw_create_count_trigger; fw_device.hip "CountTrigger over time windows").  The
 // trigger's count rides in Entry::meta above FW_CT_SHIFT (bit 0, FW_TIMER, stays clear: this trigger registers no timer
 // at maxTimestamp, so k_fire only drops such an entry at its cleanup time).  A push is one item per (record, window
@@ -584,11 +580,6 @@ int launch_ct_group(const DevCfg& c, int64_t items, const CtBuf& b, DevTable tb,
 // scan, rows, fold (the row buffer holds ctr[3] more rows)
 void launch_ct_fire(const DevCfg& c, const int64_t* val, int64_t items, const CtBuf& b, int half, DevTable tb,
                     DevRows out, Status* st, hipStream_t_ s);
-void launch_ct_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t_ s);
-void launch_ct_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, StateCols out, int64_t* tcount,
-                        unsigned long long* count, hipStream_t_ s);
-void launch_ct_restore(const DevCfg& c, int32_t kg, StateCols in, const int64_t* tcount, int64_t n, DevTable tb,
-                       Status* st, const int32_t* round_of, int32_t rounds, hipStream_t_ s);
 int64_t pane_nt_floor(const DevCfg& c, int64_t wm);  // host: DevCfg::nt_floor of a launch at watermark wm
 // FW_AGG_HLL: fold the batch's records into the registers of their (key, window) entries (after aggregate)
 void launch_hll_update(const DevCfg& c, const PRec* part, const uint32_t* offs, int32_t T, int64_t n, DevTable tb,
@@ -621,7 +612,6 @@ void launch_count_restore_check(const DevCount& cw, CountStateCols src, int64_t 
 void launch_count_restore_apply(const DevCount& cw, int32_t kg, CountStateCols src, const int64_t* eoff, int64_t n,
                                 Status* st, hipStream_t_ s);
 void launch_rehash(const DevCfg& old_c, DevTable old_t, const DevCfg& new_c, DevTable new_t, hipStream_t_ s);
-void launch_table_stats(const DevCfg& c, DevTable tb, unsigned long long* out3, hipStream_t_ s);
 void launch_reset_regions(const DevCfg& c, DevTable tb, hipStream_t_ s);
 // HyperLogLog partials (combining): pass 1 counts each partial's non-zero registers into cnt[0, n) and scans it in
 // place (cnt[n] = total; scan_tmp: launch_scan's for n + 1 words); pass 2 writes them at those offsets and frees the
@@ -648,12 +638,20 @@ void launch_dt_restore_runs(const DevCfg& c, int32_t kg, StateCols in, int64_t n
 void launch_block_export(const DevCfg& c, const int64_t* blk, int64_t n, uint8_t* acc, hipStream_t_ s);
 void launch_pool_take(const DevCfg& c, int32_t h, int32_t take, int64_t bump, int64_t n, int64_t* ids, hipStream_t_ s);
 void launch_pool_give(const DevCfg& c, const int64_t* ids, int64_t n, int32_t h, hipStream_t_ s);
-void launch_snapshot(const DevCfg& c, DevTable tb, int32_t p0, int32_t np, StateCols out, unsigned long long* count,
-                     hipStream_t_ s);
-// demand != NULL: count rows per partition (and key-group errors); NULL: insert the rows
-// (insertion: round_of[i] = the row's round, rows with the same (key, window) in different rounds; NULL = one)
-void launch_restore(const DevCfg& c, int32_t kg, StateCols in, int64_t n, int32_t* demand, DevTable tb, Status* st,
-                    const int32_t* round_of, int32_t rounds, hipStream_t_ s);
+// keyed state of a handle whose trigger is `trig`.  extra = the column beside the rows: the fire time per row
+// (Long.MIN_VALUE = null; the timer column's bit 0 = maxTimestamp's timer, bit 1 = the timer at the fire time) for
+// TRIG_CONTINUOUS, the trigger's count for TRIG_COUNT, NULL for TRIG_EVENT_TIME.
+// snapshot: the rows of partitions [p0, p0 + np), *count of them
+void launch_snapshot(const DevCfg& c, TrigKind trig, DevTable tb, int32_t p0, int32_t np, StateCols out, int64_t* extra,
+                     unsigned long long* count, hipStream_t_ s);
+// restore, first the rows per partition (and key-group errors), then their insertion: round_of[i] = the row's round,
+// rows with the same (key, window) in different rounds; NULL = one
+void launch_restore_count(const DevCfg& c, int32_t kg, StateCols in, int64_t n, int32_t* demand, Status* st,
+                          hipStream_t_ s);
+void launch_restore(const DevCfg& c, TrigKind trig, int32_t kg, StateCols in, const int64_t* extra, int64_t n,
+                    DevTable tb, Status* st, const int32_t* round_of, int32_t rounds, hipStream_t_ s);
+// out3 = {live entries, event-time timers}
+void launch_table_stats(const DevCfg& c, TrigKind trig, DevTable tb, unsigned long long* out3, hipStream_t_ s);
 void launch_key_groups(const int64_t* key, const int32_t* kh, int32_t key_kind, int64_t n, int32_t max_par,
                        int32_t* kg, hipStream_t_ s);
 void launch_route(const int64_t* key, const int64_t* ts, const int64_t* val, const int32_t* kh, int32_t key_kind,

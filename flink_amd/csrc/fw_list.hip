@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "../../include/flink_window.h"
+#include "fw_keygroup.h"
 #include "fw_range.h"
 
 namespace {
@@ -2680,24 +2681,9 @@ int push_device(fw_list* op, const int64_t* key, const int64_t* ts, const int64_
   return maybe_compact(op);
 }
 
-// the key group of a Long / Integer key: MathUtils.murmurHash of its hashCode (host restatement) % maxParallelism
+// the key group of a Long / Integer key
 int32_t host_key_group(const LCfg& cfg, int64_t k) {
-  const int32_t h = cfg.key_kind == FW_KEY_INT ? (int32_t)k : (int32_t)(k ^ (int64_t)((uint64_t)k >> 32));
-  uint32_t c = (uint32_t)h;
-  c *= 0xcc9e2d51u;
-  c = (c << 15) | (c >> 17);
-  c *= 0x1b873593u;
-  c = (c << 13) | (c >> 19);
-  c = c * 5u + 0xe6546b64u;
-  c ^= 4u;
-  c ^= c >> 16;
-  c *= 0x85ebca6bu;
-  c ^= c >> 13;
-  c *= 0xc2b2ae35u;
-  c ^= c >> 16;
-  int32_t r = (int32_t)c;
-  r = r >= 0 ? r : (r != INT32_MIN ? -r : 0);
-  return r % cfg.max_par;
+  return ::host_key_group(host_key_hash(k, cfg.key_kind == FW_KEY_INT), cfg.max_par);
 }
 
 

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/flink_window.h"
+#include "fw_keygroup.h"
 
 namespace {
 
@@ -835,24 +836,6 @@ __global__ __launch_bounds__(256) void k_ov_restore_rows(OCfg c, OMap m, ORowsD 
   for (int j = 0; j < c.nc; j++) st.cols[(int64_t)j * st.cap + d] = cols[i * c.nc + j];
 }
 
-int32_t host_kg(int32_t kind, int64_t key, int32_t max_par) {
-  const int32_t h = kind == FW_KEY_INT ? (int32_t)key : (int32_t)(key ^ (int64_t)((uint64_t)key >> 32));
-  uint32_t c = (uint32_t)h;
-  c *= 0xcc9e2d51u;
-  c = (c << 15) | (c >> 17);
-  c *= 0x1b873593u;
-  c = (c << 13) | (c >> 19);
-  c = c * 5u + 0xe6546b64u;
-  c ^= 4u;
-  c ^= c >> 16;
-  c *= 0x85ebca6bu;
-  c ^= c >> 13;
-  c *= 0xc2b2ae35u;
-  c ^= c >> 16;
-  const int32_t r = (int32_t)c;
-  return (r >= 0 ? r : (r != INT32_MIN ? -r : 0)) % max_par;
-}
-
 struct Buf {  // scratch that only grows; contents are not kept
   void* p = nullptr;
   size_t cap = 0;
@@ -1621,7 +1604,8 @@ int fw_over_restore_key_group(fw_over* op, int32_t kg, const fw_over_state* src,
   for (int64_t i = 0; i < n_keys; i++) {
     if (src->n_rows[i] < 0) return set_err(op, FW_ERR_ARG, "negative n_rows");
     total += src->n_rows[i];
-    if (c.key_kind != FW_KEY_HASHED && host_kg(c.key_kind, src->key[i], c.max_par) != kg)
+    if (c.key_kind != FW_KEY_HASHED &&
+        host_key_group(host_key_hash(src->key[i], c.key_kind == FW_KEY_INT), c.max_par) != kg)
       return set_err(op, FW_ERR_KEY_GROUP, "key %lld is not in key group %d", (long long)src->key[i], kg);
   }
   if (total != n_rows) return set_err(op, FW_ERR_ARG, "n_rows does not match the keys' row counts");

@@ -32,6 +32,7 @@
 #include "../../include/flink_window.h"
 #include "fw_cont.h"
 #include "fw_internal.h"
+#include "fw_keygroup.h"
 #include "fw_range.h"
 
 namespace {
@@ -171,6 +172,11 @@ struct fw_op {
 };
 
 namespace {
+
+// the trigger whose state the handle's entries carry (the keyed-state kernels' instantiation)
+TrigKind trig_kind(const fw_op* op) {
+  return cont_iv(op->dc) ? TRIG_CONTINUOUS : op->ct.nfire ? TRIG_COUNT : TRIG_EVENT_TIME;
+}
 
 int set_err(fw_op* op, int code, const char* fmt, ...) {
   char buf[512];
@@ -2160,12 +2166,7 @@ int fw_get_stats(fw_op* op, fw_stats* o) {
   int rc = settle(op);
   if (rc) return rc;
   HIP_OR_RETURN(op, hipMemsetAsync(op->d_stats3, 0, 4 * sizeof(unsigned long long), op->stream));
-  if (cont_iv(op->dc))
-    fwdev::launch_cont_stats(op->dc, op->tb, op->d_stats3, op->stream);
-  else if (op->ct.nfire)
-    fwdev::launch_ct_stats(op->dc, op->tb, op->d_stats3, op->stream);
-  else
-    fwdev::launch_table_stats(op->dc, op->tb, op->d_stats3, op->stream);
+  fwdev::launch_table_stats(op->dc, trig_kind(op), op->tb, op->d_stats3, op->stream);
   unsigned long long h3[4];
   HIP_OR_RETURN(op, hipMemcpyAsync(h3, op->d_stats3, sizeof h3, hipMemcpyDeviceToHost, op->stream));
   if ((rc = sync_status(op))) return rc;
@@ -2429,24 +2430,6 @@ int alloc_state_cols(fw_op* op, StateCols& c, int64_t n) {
   for (int i = 0; i < 8; i++) HIP_OR_RETURN(op, dmalloc(cols[i], (size_t)std::max<int64_t>(n, 1)));
   return FW_OK;
 }
-// KeyGroupRangeAssignment.computeKeyGroupForKeyHash on the host: MathUtils.murmurHash(hash) % maxParallelism
-// (MathUtils.java:134-154; the device's is fw_jmath.h key_group)
-int32_t host_key_group(int32_t hash, int32_t max_par) {
-  uint32_t c = (uint32_t)hash;
-  c *= 0xcc9e2d51u;
-  c = (c << 15) | (c >> 17);
-  c *= 0x1b873593u;
-  c = (c << 13) | (c >> 19);
-  c = c * 5u + 0xe6546b64u;
-  c ^= 4u;
-  c ^= c >> 16;
-  c *= 0x85ebca6bu;
-  c ^= c >> 13;
-  c *= 0xc2b2ae35u;
-  c ^= c >> 16;
-  const int32_t r = (int32_t)c;
-  return (r >= 0 ? r : (r != INT32_MIN ? -r : 0)) % max_par;
-}
 void free_state_cols(StateCols& c) {
   int64_t** cols[8] = {&c.key, &c.start, &c.end, &c.cnt, &c.sum, &c.mn, &c.mx, &c.timer};
   for (int i = 0; i < 8; i++) dfree(*cols[i]);
@@ -2468,7 +2451,7 @@ int fw_snapshot_key_group(fw_op* op, int32_t kg, const fw_state_rows* dst, int64
   return fw_snapshot_key_group_blocks(op, kg, dst, nullptr, cap, n);
 }
 
-static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, uint8_t* blocks, int64_t* fire,
+static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, uint8_t* blocks, int64_t* extra,
                              int64_t cap, int64_t* n);
 int fw_snapshot_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* dst, uint8_t* blocks, int64_t cap,
                                  int64_t* n) {
@@ -2496,9 +2479,9 @@ int fw_snapshot_key_group_fire(fw_op* op, int32_t kg, const fw_state_rows* dst, 
   if (op && dst && cap > 0 && !fire) return set_err(op, FW_ERR_ARG, "null fire_time column");
   return snapshot_rows_any(op, kg, dst, nullptr, fire, cap, n);
 }
-// the rows of key group kg (fire != NULL: a ContinuousEventTimeTrigger handle's, with their fire times, or a
-// CountTrigger handle's, with their trigger counts)
-static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, uint8_t* blocks, int64_t* fire,
+// the rows of key group kg (extra: the column beside them, a ContinuousEventTimeTrigger handle's fire times or a
+// CountTrigger handle's trigger counts; NULL for the others)
+static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, uint8_t* blocks, int64_t* extra,
                              int64_t cap, int64_t* n) {
   if (op && op->cfg.assigner == FW_COUNT)
     return set_err(op, FW_ERR_UNSUPPORTED, "keyed-state snapshots of count windows are not offered");
@@ -2519,28 +2502,23 @@ static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, ui
   for (int32_t v : live) bound += v;
   StateCols d{};
   uint8_t* acc = nullptr;
-  int64_t* dfire = nullptr;
-  const bool ct = op->ct.nfire != 0;
-  const bool cont = cont_iv(c) != 0 || ct;  // (an extra column beside the rows)
+  int64_t* dextra = nullptr;
+  const TrigKind trig = trig_kind(op);
   auto release = [&]() {
     free_state_cols(d);
     dfree(d.blk);
     dfree(acc);
-    dfree(dfire);
+    dfree(dextra);
   };
   if ((rc = alloc_state_cols(op, d, bound)) ||
-      (cont && dmalloc(&dfire, (size_t)std::max<int64_t>(bound, 1)) != hipSuccess && (rc = FW_ERR_HIP)) ||
+      (trig != TRIG_EVENT_TIME && dmalloc(&dextra, (size_t)std::max<int64_t>(bound, 1)) != hipSuccess &&
+       (rc = FW_ERR_HIP)) ||
       (bb && dmalloc(&d.blk, (size_t)std::max<int64_t>(bound, 1)) != hipSuccess && (rc = FW_ERR_HIP))) {
     release();
     return rc == FW_ERR_HIP ? set_err(op, rc, "snapshot: allocation failed") : rc;
   }
   HIP_OR_RETURN(op, hipMemsetAsync(op->d_stats3, 0, sizeof(unsigned long long), op->stream));
-  if (ct)
-    fwdev::launch_ct_snapshot(c, op->tb, p0, np, d, dfire, op->d_stats3, op->stream);
-  else if (cont)
-    fwdev::launch_cont_snapshot(c, op->tb, p0, np, d, dfire, op->d_stats3, op->stream);
-  else
-    fwdev::launch_snapshot(c, op->tb, p0, np, d, op->d_stats3, op->stream);
+  fwdev::launch_snapshot(c, trig, op->tb, p0, np, d, dextra, op->d_stats3, op->stream);
   unsigned long long got = 0;
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(&got, op->d_stats3, sizeof got, hipMemcpyDeviceToHost, op->stream);
@@ -2550,8 +2528,8 @@ static int snapshot_rows_any(fw_op* op, int32_t kg, const fw_state_rows* dst, ui
     int64_t* ds[8] = {d.key, d.start, d.end, d.cnt, d.sum, d.mn, d.mx, d.timer};
     for (int i = 0; i < 8 && e == hipSuccess; i++)
       if (hs[i]) e = hipMemcpyAsync(hs[i], ds[i], got * sizeof(int64_t), hipMemcpyDeviceToHost, op->stream);
-    if (e == hipSuccess && cont && fire)
-      e = hipMemcpyAsync(fire, dfire, got * sizeof(int64_t), hipMemcpyDeviceToHost, op->stream);
+    if (e == hipSuccess && dextra && extra)
+      e = hipMemcpyAsync(extra, dextra, got * sizeof(int64_t), hipMemcpyDeviceToHost, op->stream);
     if (e == hipSuccess && bb) {  // the rows' accumulators in their snapshot form
       e = dmalloc(&acc, (size_t)(got * bb));
       if (e == hipSuccess) {
@@ -2631,7 +2609,7 @@ int fw_restore_key_group(fw_op* op, int32_t kg, const fw_state_rows* src, int64_
 }
 
 static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, const uint8_t* blocks,
-                            const int64_t* fire, int64_t n);
+                            const int64_t* extra, int64_t n);
 int fw_restore_key_group_blocks(fw_op* op, int32_t kg, const fw_state_rows* src, const uint8_t* blocks, int64_t n) {
   if (op && cont_iv(op->dc))
     return set_err(op, FW_ERR_UNSUPPORTED, "a ContinuousEventTimeTrigger handle's windows carry the trigger's fire time "
@@ -2657,9 +2635,9 @@ int fw_restore_key_group_fire(fw_op* op, int32_t kg, const fw_state_rows* src, c
   if (op && n > 0 && !fire) return set_err(op, FW_ERR_ARG, "null fire_time column");
   return restore_rows_any(op, kg, src, nullptr, fire, n);
 }
-// (fire != NULL: a ContinuousEventTimeTrigger handle's rows, with their fire times)
+// (extra: the column beside the rows, as in snapshot_rows_any)
 static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, const uint8_t* blocks,
-                            const int64_t* fire, int64_t n) {
+                            const int64_t* extra, int64_t n) {
   if (op && op->cfg.assigner == FW_COUNT)
     return set_err(op, FW_ERR_UNSUPPORTED, "keyed-state snapshots of count windows are not offered");
   if (!op || (n > 0 && !src) || n < 0) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
@@ -2672,33 +2650,29 @@ static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, con
   const int64_t* hs[8] = {src->key, src->start, src->end, src->count, src->sum, src->min, src->max, src->timer};
   for (const int64_t* h : hs)
     if (!h) return set_err(op, FW_ERR_ARG, "null state column");
-  const bool ct = op->ct.nfire != 0;
-  if (ct) {  // the rows as fw_snapshot_key_group_trigger_count writes them, checked before anything changes
-    for (int64_t i = 0; i < n; i++) {
-      if (src->count[i] < 0 || src->end[i] != (int64_t)((uint64_t)src->start[i] + (uint64_t)op->dc.size))
-        return set_err(op, FW_ERR_ARG, "restore: row %lld is not a window of this operator's size", (long long)i);
-      if (fire[i] < 0 || fire[i] >= (int64_t(1) << 48))
+  // a trigger handle's rows as its snapshot writes them (fw_snapshot_key_group_fire / _trigger_count), checked before
+  // anything changes
+  const TrigKind trig = trig_kind(op);
+  const int64_t span = trig == TRIG_CONTINUOUS ? op->dc.size + op->dc.lateness + 2 * cont_iv(op->dc) : 0;
+  for (int64_t i = 0; i < n && trig != TRIG_EVENT_TIME; i++) {
+    if (trig == TRIG_CONTINUOUS && (src->timer[i] & ~(int64_t)3))
+      return set_err(op, FW_ERR_ARG, "restore: row %lld: the timer column holds bit 0 (maxTimestamp's timer) and bit 1 "
+                                     "(the timer at the fire time)", (long long)i);
+    if (src->count[i] < 0 || src->end[i] != (int64_t)((uint64_t)src->start[i] + (uint64_t)op->dc.size))
+      return set_err(op, FW_ERR_ARG, "restore: row %lld is not a window of this operator's size", (long long)i);
+    if (trig == TRIG_COUNT) {
+      if (extra[i] < 0 || extra[i] >= (int64_t(1) << 48))
         return set_err(op, FW_ERR_ARG, "restore: row %lld: trigger count %lld is not in [0, 2^48)", (long long)i,
-                       (long long)fire[i]);
+                       (long long)extra[i]);
+      continue;
     }
-  }
-  const bool cont = cont_iv(op->dc) != 0;
-  if (cont) {  // the rows as fw_snapshot_key_group_fire writes them, checked before anything changes
-    const int64_t iv = cont_iv(op->dc);
-    for (int64_t i = 0; i < n; i++) {
-      if (src->timer[i] & ~(int64_t)3)
-        return set_err(op, FW_ERR_ARG, "restore: row %lld: the timer column holds bit 0 (maxTimestamp's timer) and bit 1 "
-                                       "(the timer at the fire time)", (long long)i);
-      if (src->count[i] < 0 || src->end[i] != (int64_t)((uint64_t)src->start[i] + (uint64_t)op->dc.size))
-        return set_err(op, FW_ERR_ARG, "restore: row %lld is not a window of this operator's size", (long long)i);
-      const int64_t d = (int64_t)((uint64_t)fire[i] - (uint64_t)src->start[i]), span = op->dc.size + op->dc.lateness + 2 * iv;
-      if (fire[i] != INT64_MIN && (d > span || d < -span))
-        return set_err(op, FW_ERR_ARG, "restore: row %lld: fire time %lld is not one this trigger reaches in window "
-                                       "[%lld, %lld)", (long long)i, (long long)fire[i], (long long)src->start[i],
-                       (long long)src->end[i]);
-      if (fire[i] == INT64_MIN && (src->timer[i] & 2))
-        return set_err(op, FW_ERR_ARG, "restore: row %lld registers a timer at a null fire time", (long long)i);
-    }
+    const int64_t d = (int64_t)((uint64_t)extra[i] - (uint64_t)src->start[i]);
+    if (extra[i] != INT64_MIN && (d > span || d < -span))
+      return set_err(op, FW_ERR_ARG, "restore: row %lld: fire time %lld is not one this trigger reaches in window "
+                                     "[%lld, %lld)", (long long)i, (long long)extra[i], (long long)src->start[i],
+                     (long long)src->end[i]);
+    if (extra[i] == INT64_MIN && (src->timer[i] & 2))
+      return set_err(op, FW_ERR_ARG, "restore: row %lld registers a timer at a null fire time", (long long)i);
   }
   // first-element reduces: records pushed after the restore are numbered after every restored first
   // element, so the earlier element keeps winning in the caller's numbering
@@ -2729,10 +2703,10 @@ static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, con
   StateCols d{};
   int32_t* demand = nullptr;
   uint8_t* acc = nullptr;
-  int64_t* dfire = nullptr;
+  int64_t* dextra = nullptr;
   auto fail = [&](int code) {
     free_state_cols(d);
-    dfree(dfire);
+    dfree(dextra);
     dfree(demand);
     dfree(acc);
     dfree(d.blk);
@@ -2744,14 +2718,15 @@ static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, con
   for (int i = 0; i < 8; i++)
     if (hipMemcpyAsync(ds[i], hs[i], n * sizeof(int64_t), hipMemcpyHostToDevice, op->stream) != hipSuccess)
       return fail(set_err(op, FW_ERR_HIP, "restore: copy failed"));
-  if ((cont || ct) && (dmalloc(&dfire, (size_t)n) != hipSuccess ||
-               hipMemcpyAsync(dfire, fire, n * sizeof(int64_t), hipMemcpyHostToDevice, op->stream) != hipSuccess))
+  if (trig != TRIG_EVENT_TIME &&
+      (dmalloc(&dextra, (size_t)n) != hipSuccess ||
+       hipMemcpyAsync(dextra, extra, n * sizeof(int64_t), hipMemcpyHostToDevice, op->stream) != hipSuccess))
     return fail(set_err(op, FW_ERR_HIP, "restore: copy failed"));
   // the rows' demand per partition: grow the table first if a region would pass its load limit
   const int32_t P = op->dc.P;
   if (dmalloc(&demand, (size_t)P) != hipSuccess || hipMemsetAsync(demand, 0, P * sizeof(int32_t), op->stream) != hipSuccess)
     return fail(set_err(op, FW_ERR_HIP, "restore: allocation failed"));
-  fwdev::launch_restore(op->dc, kg, d, n, demand, op->tb, op->d_status, nullptr, 0, op->stream);
+  fwdev::launch_restore_count(op->dc, kg, d, n, demand, op->d_status, op->stream);
   std::vector<int32_t> dem(P), live(P);
   if (hipMemcpyAsync(dem.data(), demand, P * sizeof(int32_t), hipMemcpyDeviceToHost, op->stream) != hipSuccess ||
       hipMemcpyAsync(live.data(), op->tb.live, P * sizeof(int32_t), hipMemcpyDeviceToHost, op->stream) != hipSuccess ||
@@ -2800,12 +2775,7 @@ static int restore_rows_any(fw_op* op, int32_t kg, const fw_state_rows* src, con
         hipMemcpyAsync(d_round, round_of.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, op->stream) != hipSuccess)
       return fail(set_err(op, FW_ERR_HIP, "restore: allocation failed"));
   }
-  if (ct)
-    fwdev::launch_ct_restore(op->dc, kg, d, dfire, n, op->tb, op->d_status, d_round, rounds, op->stream);
-  else if (cont)
-    fwdev::launch_cont_restore(op->dc, kg, d, dfire, n, op->tb, op->d_status, d_round, rounds, op->stream);
-  else
-    fwdev::launch_restore(op->dc, kg, d, n, nullptr, op->tb, op->d_status, d_round, rounds, op->stream);
+  fwdev::launch_restore(op->dc, trig, kg, d, dextra, n, op->tb, op->d_status, d_round, rounds, op->stream);
   const bool launched = hipGetLastError() == hipSuccess;
   rc = sync_status(op);
   dfree(d_round);
@@ -2921,8 +2891,7 @@ int fw_count_restore_key_group(fw_op* op, int32_t kg, const fw_list_state* src, 
     eoff[(size_t)i] = total;
     total += L;
     if (op->cfg.key_kind != FW_KEY_HASHED) {  // (a hashed key's key group is the caller's word)
-      const int32_t h = op->cfg.key_kind == FW_KEY_INT ? (int32_t)k : (int32_t)(k ^ (int64_t)((uint64_t)k >> 32));
-      if (host_key_group(h, op->cfg.max_parallelism) != kg)
+      if (host_key_group(host_key_hash(k, op->cfg.key_kind == FW_KEY_INT), op->cfg.max_parallelism) != kg)
         return set_err(op, FW_ERR_KEY_GROUP, "key %lld is not in key group %d", (long long)k, kg);
     }
     if (!seen.insert(k).second)

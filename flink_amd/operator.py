@@ -530,6 +530,17 @@ class GpuWindowOperator:
         bb = N.lib().fw_state_block_bytes(self._h)
         return STATE_DTYPE if bb == 0 else np.dtype(STATE_DTYPE.descr + [("acc", "u1", (bb,))])
 
+    def _state_calls(self):
+        """(native snapshot function, native restore function, the field that rides beside STATE_FIELDS or None): the
+        trigger's int64 column, or the `acc` blocks of the block-pool aggregates"""
+        L = N.lib()
+        if self._continuous:
+            return L.fw_snapshot_key_group_fire, L.fw_restore_key_group_fire, "fire_time"
+        if self._counting:
+            return L.fw_snapshot_key_group_trigger_count, L.fw_restore_key_group_trigger_count, "trigger_count"
+        bb = L.fw_state_block_bytes(self._h)
+        return L.fw_snapshot_key_group_blocks, L.fw_restore_key_group_blocks, "acc" if bb else None
+
     def snapshot_key_group(self, kg):
         """Live (key, window) accumulators of key group kg as a state_dtype() array (no order).  Count windows:
         (lists LIST_STATE_DTYPE, elements ELEM_DTYPE concatenated in list order), each key's trigger count and the
@@ -552,34 +563,19 @@ class GpuWindowOperator:
             for f in ec:
                 el[f] = ec[f]
             return lists, el
-        if self._continuous or self._counting:
-            extra = "fire_time" if self._continuous else "trigger_count"
-            snap = L.fw_snapshot_key_group_fire if self._continuous else L.fw_snapshot_key_group_trigger_count
-            n = ctypes.c_int64()
-            N.check(snap(self._h, int(kg), None, None, 0, ctypes.byref(n)), self._h)
-            cols = {f: np.zeros(n.value, dtype=np.int64) for f in STATE_FIELDS + (extra,)}
-            dst = N.FwStateRows(**{f: cols[f].ctypes.data for f in STATE_FIELDS})
-            got = ctypes.c_int64()
-            N.check(snap(self._h, int(kg), ctypes.byref(dst), cols[extra].ctypes.data, n.value, ctypes.byref(got)),
-                    self._h)
-            out = np.zeros(got.value, dtype=self.state_dtype())
-            for f in cols:
-                out[f] = cols[f][:got.value]
-            return out
-        bb = L.fw_state_block_bytes(self._h)
+        snap, _, extra = self._state_calls()
         n = ctypes.c_int64()
-        N.check(L.fw_snapshot_key_group_blocks(self._h, int(kg), None, None, 0, ctypes.byref(n)), self._h)
+        N.check(snap(self._h, int(kg), None, None, 0, ctypes.byref(n)), self._h)
         cols = {f: np.zeros(n.value, dtype=np.int64) for f in STATE_FIELDS}
-        acc = np.zeros((n.value, max(bb, 1)), dtype=np.uint8)
+        if extra:  # (a sub-array field's rows: `acc` gives n x block bytes)
+            cols[extra] = np.zeros(n.value, dtype=self.state_dtype()[extra])
         dst = N.FwStateRows(**{f: cols[f].ctypes.data for f in STATE_FIELDS})
         got = ctypes.c_int64()
-        N.check(L.fw_snapshot_key_group_blocks(self._h, int(kg), ctypes.byref(dst), acc.ctypes.data if bb else None,
-                                               n.value, ctypes.byref(got)), self._h)
+        N.check(snap(self._h, int(kg), ctypes.byref(dst), cols[extra].ctypes.data if extra else None, n.value,
+                     ctypes.byref(got)), self._h)
         out = np.zeros(got.value, dtype=self.state_dtype())
-        for f in STATE_FIELDS:
+        for f in cols:
             out[f] = cols[f][:got.value]
-        if bb:
-            out["acc"] = acc[:got.value]
         return out
 
     def snapshot_state(self):
@@ -602,25 +598,21 @@ class GpuWindowOperator:
             return
         if elems is not None:
             raise ValueError("only count windows restore (lists, elems); this operator restores state_dtype() rows")
-        if self._continuous or self._counting:
-            extra = "fire_time" if self._continuous else "trigger_count"
-            restore = L.fw_restore_key_group_fire if self._continuous else L.fw_restore_key_group_trigger_count
-            rows = np.ascontiguousarray(rows)
-            if rows.dtype.names is None or extra not in rows.dtype.names:
-                raise ValueError(f"rows of this operator carry `{extra}` (state_dtype())")
-            cols = {f: np.ascontiguousarray(rows[f], dtype=np.int64) for f in STATE_FIELDS + (extra,)}
-            src = N.FwStateRows(**{f: cols[f].ctypes.data for f in STATE_FIELDS})
-            N.check(restore(self._h, int(kg), ctypes.byref(src), cols[extra].ctypes.data, len(rows)), self._h)
-            return
-        bb = L.fw_state_block_bytes(self._h)
+        _, restore, extra = self._state_calls()
         rows = np.ascontiguousarray(rows)
-        if bb and (rows.dtype.names is None or "acc" not in rows.dtype.names or rows.dtype["acc"].shape != (bb,)):
-            raise ValueError(f"rows of this aggregate carry `acc` blocks of {bb} bytes (state_dtype())")
+        names = rows.dtype.names or ()
+        if extra == "acc":
+            bb = self.state_dtype()["acc"].shape[0]
+            if "acc" not in names or rows.dtype["acc"].shape != (bb,):
+                raise ValueError(f"rows of this aggregate carry `acc` blocks of {bb} bytes (state_dtype())")
+        elif extra and extra not in names:
+            raise ValueError(f"rows of this operator carry `{extra}` (state_dtype())")
         cols = {f: np.ascontiguousarray(rows[f], dtype=np.int64) for f in STATE_FIELDS}
-        acc = np.ascontiguousarray(rows["acc"], dtype=np.uint8) if bb else None
+        if extra:
+            cols[extra] = np.ascontiguousarray(rows[extra], dtype=self.state_dtype()[extra].base)
         src = N.FwStateRows(**{f: cols[f].ctypes.data for f in STATE_FIELDS})
-        N.check(L.fw_restore_key_group_blocks(self._h, int(kg), ctypes.byref(src),
-                                              acc.ctypes.data if bb and len(rows) else None, len(rows)), self._h)
+        N.check(restore(self._h, int(kg), ctypes.byref(src), cols[extra].ctypes.data if extra and len(rows) else None,
+                        len(rows)), self._h)
 
     def initialize_state(self, snapshot):
         """Restores the key groups of `snapshot` ({kg: rows}) that this operator owns; others are skipped,

@@ -279,6 +279,51 @@ def _kg(key, max_par=128):
     return assign_to_key_group(long_hash_code(key), max_par)
 
 
+# rows of one window [0, 100) as (count, sum, min, max, timer, fire_time); the first one is an emptied window whose
+# sum / min / max are junk a restore must not read
+_MERGE_ROWS = [(0, 999, -777, 888, 0b10, 30), (3, 60, 10, 30, 0b01, 20), (2, -5, -7, 2, 0b10, 20),
+               (4, 100, 1, 50, 0b01, FIRE_NULL)]
+_NULL_ROWS = [(1, 8, 8, 8, 0b01, FIRE_NULL), (2, 11, 5, 6, 0b00, FIRE_NULL)]
+
+
+def _merged(rows):
+    """what the rows of one (key, window) restore to: AggregateFunction.merge of the rows with contents, the fire time
+    by Min over the non-null ones, maxTimestamp's timer if any row has it, the fire timer of the rows at that Min"""
+    full = [r for r in rows if r[0] > 0]
+    fires = [r[5] for r in rows if r[5] != FIRE_NULL]
+    fire = min(fires) if fires else FIRE_NULL
+    timer = int(any(r[4] & 1 for r in rows)) | 2 * int(any(r[4] & 2 for r in rows if fires and r[5] == fire))
+    return (sum(r[0] for r in full), sum(r[1] for r in full), min((r[2] for r in full), default=None),
+            max((r[3] for r in full), default=None), timer, fire)
+
+
+@pytest.mark.parametrize("lateness", [0, 30])
+def test_gpu_agg_continuous_restore_merges_repeated_rows(lateness):
+    """rows of one (key, window) merge on restore, within one call (a round per repetition) and onto a window an
+    earlier call restored: key 1 in one call with the emptied row first (it is the one inserted), key 2 in two calls
+    with the emptied row merging, key 3 with null fire times only, key 4 an emptied window alone"""
+    gpu = _Gpu("long", assigner="tumbling", size=100, interval=10, lateness=lateness)
+    calls = [(1, _MERGE_ROWS), (2, _MERGE_ROWS[2:]), (2, _MERGE_ROWS[:2]), (3, _NULL_ROWS), (4, _MERGE_ROWS[:1])]
+    for key, rows in calls:
+        a = np.zeros(len(rows), dtype=gpu.op.state_dtype())
+        for i, (cnt, sm, mn, mx, timer, fire) in enumerate(rows):
+            a[i] = (key, 0, 100, cnt, sm, mn, mx, timer, fire)
+        gpu.op.restore_key_group(_kg(key), a)
+    exp = {1: _merged(_MERGE_ROWS), 2: _merged(_MERGE_ROWS), 3: _merged(_NULL_ROWS), 4: _merged(_MERGE_ROWS[:1])}
+    assert exp[1] == (9, 155, -7, 50, 0b11, 20) and exp[3][4:] == (0b01, FIRE_NULL) and exp[4][0] == 0
+    back = np.concatenate(list(gpu.op.snapshot_state().values()))
+    back = back[np.argsort(back["key"])]
+    assert back["key"].tolist() == [1, 2, 3, 4]  # one row per (key, window)
+    assert back["start"].tolist() == [0] * 4 and back["end"].tolist() == [100] * 4
+    for r in back:
+        cnt, sm, mn, mx, timer, fire = exp[int(r["key"])]
+        assert (int(r["count"]), int(r["timer"]), int(r["fire_time"])) == (cnt, timer, fire), int(r["key"])
+        if cnt:  # (an emptied window's sum / min / max are not state)
+            assert (int(r["sum"]), int(r["min"]), int(r["max"])) == (sm, mn, mx), int(r["key"])
+    assert gpu.op.stats()["keyed_state_entries"] == sum(1 for e in exp.values() if e[0] > 0) == 3
+    gpu.close()
+
+
 def test_gpu_agg_continuous_combiner_refused():
     gpu = _Gpu(assigner="tumbling", size=100, interval=10)
     with pytest.raises(N.NativeError) as e:

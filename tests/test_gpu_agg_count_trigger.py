@@ -371,6 +371,28 @@ def test_gpu_agg_count_trigger_restored_count_above_n():
     gpu.close()
 
 
+def test_gpu_agg_count_trigger_restored_empty_duplicate():
+    """a duplicate row of an emptied window (count 0, junk in sum / min / max) leaves the accumulator as it is and
+    adds its trigger count, whether it is the row that is inserted (key 1) or the one that merges (key 2)"""
+    cfg = dict(assigner="tumbling", size=100, slide=0, offset=0, lateness=0, n=4, purging=True, side_output=False)
+    gpu = _Gpu("long", **cfg)
+    rows = np.zeros(4, dtype=gpu.op.state_dtype())
+    for i, (key, cnt, sm, mn, mx, tc) in enumerate([(1, 0, 999, -777, 888, 1), (1, 5, 50, 2, 30, 2),
+                                                    (2, 3, -8, -9, 3, 1), (2, 0, 999, -777, 888, 2)]):
+        rows[i] = (key, 0, 100, cnt, sm, mn, mx, 0, tc)
+    from oracle.oracle import key_groups_long
+    kgs = key_groups_long(rows["key"], 128)
+    for g in np.unique(kgs):
+        gpu.op.restore_key_group(int(g), rows[kgs == g])
+    back = np.concatenate(list(gpu.op.snapshot_state().values()))
+    back = back[np.argsort(back["key"])]
+    assert back["key"].tolist() == [1, 2] and back["trigger_count"].tolist() == [3, 3]
+    assert back["count"].tolist() == [5, 3] and back["sum"].tolist() == [50, -8]
+    assert back["min"].tolist() == [2, -9] and back["max"].tolist() == [30, 3]
+    assert gpu.op.stats()["keyed_state_entries"] == 2
+    gpu.close()
+
+
 def test_gpu_agg_count_trigger_neighbours_unchanged():
     """a tumbling and a sliding handle of plain fw_create still give the oracle's rows beside a CountTrigger handle"""
     ct = _Gpu("long", **U.CONFIGS[1])
