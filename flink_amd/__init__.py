@@ -32,4 +32,7 @@ def __getattr__(name):
     if name in ("OverAggregate", "Over"):
         from . import over
         return getattr(over, name)
+    if name in ("TimeBoundedJoin", "TJOIN_ROW_DTYPE"):
+        from . import timejoin
+        return getattr(timejoin, name)
     raise AttributeError(name)

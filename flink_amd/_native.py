@@ -181,6 +181,33 @@ def fw_over_acc_words(columns):
     return 1 + 5 * columns
 
 
+FW_TJOIN_INNER, FW_TJOIN_LEFT, FW_TJOIN_RIGHT, FW_TJOIN_FULL = 0, 1, 2, 3
+
+
+class FwTjoinConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("join_type", "key_kind", "max_parallelism", "key_group_start",
+                                              "key_group_end", "device")] + \
+        [(n, ctypes.c_int64) for n in ("lower", "upper", "allowed_lateness", "expected_keys", "max_batch",
+                                       "max_pairs")]
+
+
+class FwTjoinRows(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("key", "left_ord", "right_ord", "left_rowtime", "right_rowtime",
+                                               "left_val", "right_val", "cause_ord", "timer_ts")]
+
+
+class FwTjoinStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "rows_in", "cached_rows", "rows_not_cached", "pairs", "padded_at_arrival", "padded_at_scan",
+        "padded_at_timer", "pairs_with_expired_rows", "gate_skips", "timers_set", "store_rows", "active_timers",
+        "current_watermark", "pending_output_rows")]
+
+
+class FwTjoinState(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("key", "left_timer", "right_timer", "n_rows", "side", "rowtime",
+                                               "ordinal", "val", "emitted")]
+
+
 # every exported symbol with its ctypes signature (restype, argtypes); mirrors include/flink_window.h
 SIGNATURES = {
     "fw_create": (ctypes.c_int, [ctypes.POINTER(FwConfig), ctypes.POINTER(VP)]),
@@ -299,6 +326,20 @@ SIGNATURES = {
                                                   ctypes.c_int64, I64P, I64P]),
     "fw_over_restore_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwOverState), ctypes.c_int64,
                                                  ctypes.c_int64]),
+    "fw_tjoin_create": (ctypes.c_int, [ctypes.POINTER(FwTjoinConfig), ctypes.POINTER(VP)]),
+    "fw_tjoin_destroy": (None, [VP]),
+    "fw_tjoin_last_error": (ctypes.c_char_p, [VP]),
+    "fw_tjoin_push_batch": (ctypes.c_int, [VP, VP, VP, VP, VP, VP, ctypes.c_int64]),
+    "fw_tjoin_push_batch_device": (ctypes.c_int, [VP, VP, VP, VP, VP, VP, ctypes.c_int64]),
+    "fw_tjoin_advance_watermark": (ctypes.c_int, [VP, ctypes.c_int64, I64P, I64P]),
+    "fw_tjoin_drain": (ctypes.c_int, [VP, ctypes.POINTER(FwTjoinRows), VP, ctypes.c_int64, I64P]),
+    "fw_tjoin_rows_device": (ctypes.c_int, [VP, ctypes.POINTER(FwTjoinRows), I64P]),
+    "fw_tjoin_clear_pending": (ctypes.c_int, [VP]),
+    "fw_tjoin_get_stats": (ctypes.c_int, [VP, ctypes.POINTER(FwTjoinStats)]),
+    "fw_tjoin_snapshot_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwTjoinState), ctypes.c_int64,
+                                                   ctypes.c_int64, I64P, I64P]),
+    "fw_tjoin_restore_key_group": (ctypes.c_int, [VP, ctypes.c_int32, ctypes.POINTER(FwTjoinState), ctypes.c_int64,
+                                                  ctypes.c_int64]),
     "fw_generate_device": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, VP,
                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, VP, VP, VP, VP, VP]),
 }

@@ -1051,6 +1051,123 @@ int fw_over_snapshot_key_group(fw_over* op, int32_t key_group, const fw_over_sta
 int fw_over_restore_key_group(fw_over* op, int32_t key_group, const fw_over_state* src, int64_t n_keys,
                               int64_t n_rows);
 
+/* ---- Table API time-windowed (interval) join on row time (fw_tjoin.hip) ----
+ * `l JOIN r ON l.k = r.k AND l.rowtime BETWEEN r.rowtime + lower AND r.rowtime + upper`, INNER or outer: the handle
+ * replaces FT/runtime/join/RowTimeBoundedStreamJoin.scala (TimeBoundedStreamJoin.scala:55-494) inside
+ * FT/runtime/operators/KeyedCoProcessOperatorWithWatermarkDelay.scala, as
+ * FT/plan/nodes/datastream/DataStreamWindowJoin.scala:279-330 plans it.  It joins on key and row time only; an
+ * operator with a further (non-equi) predicate stays on the CPU.  Both inputs are pushed in one tagged batch whose
+ * index order is the arrival order across both sides. */
+#define FW_TJOIN_INNER 0
+#define FW_TJOIN_LEFT 1  /* LEFT OUTER: an unjoined left row leaves null-padded  */
+#define FW_TJOIN_RIGHT 2 /* RIGHT OUTER                                          */
+#define FW_TJOIN_FULL 3  /* FULL OUTER                                           */
+
+typedef struct fw_tjoin fw_tjoin;
+typedef struct fw_tjoin_config {
+  int32_t join_type;        /* FW_TJOIN_* */
+  int32_t key_kind;         /* FW_KEY_* */
+  int32_t max_parallelism;
+  int32_t key_group_start;  /* the handle's KeyGroupRange, inclusive */
+  int32_t key_group_end;
+  int32_t device;
+  int64_t lower;            /* leftLowerBound: l.rowtime >= r.rowtime + lower                  */
+  int64_t upper;            /* leftUpperBound: l.rowtime <= r.rowtime + upper; lower <= upper   */
+  int64_t allowed_lateness; /* >= 0 (the planner passes 0)                                      */
+  int64_t expected_keys;    /* sizes the key map at creation (it grows); 0 = default            */
+  int64_t max_batch;        /* largest push the scratch is sized for (it grows); 0 = default    */
+  int64_t max_pairs;        /* most pending output rows; 0 = 2^30 (as fw_join_config)           */
+} fw_tjoin_config;
+
+/* output rows.  left_ord / right_ord: the arrival ordinals of the joined input rows, from one counter over both
+ * sides; -1 marks the null-padded side (its rowtime and val are 0).  cause_ord: the input row whose processElement
+ * emitted the row, -1 for a clean-up timer; timer_ts: that timer's time (the record's timestamp), -1 otherwise. */
+typedef struct fw_tjoin_rows {
+  int64_t* key;
+  int64_t* left_ord;
+  int64_t* right_ord;
+  int64_t* left_rowtime;
+  int64_t* right_rowtime;
+  int64_t* left_val;
+  int64_t* right_val;
+  int64_t* cause_ord;
+  int64_t* timer_ts;
+} fw_tjoin_rows;
+
+typedef struct fw_tjoin_stats {
+  int64_t rows_in;
+  int64_t cached_rows;             /* pushed rows put into a cache                                         */
+  int64_t rows_not_cached;         /* pushed rows whose window the operator time had already passed        */
+  int64_t pairs;                   /* joined rows emitted                                                  */
+  int64_t padded_at_arrival;       /* null-padded rows: an uncached, unjoined row                          */
+  int64_t padded_at_scan;          /* ... an expired, unjoined cached row met by a scanning row            */
+  int64_t padded_at_timer;         /* ... an expired, unjoined cached row at a clean-up timer              */
+  int64_t pairs_with_expired_rows; /* joined rows whose cached partner had expired (it left in that scan)  */
+  int64_t gate_skips;              /* pushed rows that did not scan the other cache                        */
+  int64_t timers_set;              /* clean-up timer registrations (arrivals and re-registrations)         */
+  int64_t store_rows;              /* rows in the two caches now                                           */
+  int64_t active_timers;           /* timer states that are set now                                        */
+  int64_t current_watermark;
+  int64_t pending_output_rows;
+} fw_tjoin_stats;
+
+/* keyed state of one key group.  Per key: left_timer / right_timer = leftTimerState / rightTimerState (0 = unset);
+ * n_rows[i] rows of key i follow each other in the row columns: side (0 = left cache, 1 = right cache), rowtime,
+ * ordinal, val, emitted (the cached tuple's flag). */
+typedef struct fw_tjoin_state {
+  int64_t* key;
+  int64_t* left_timer;
+  int64_t* right_timer;
+  int64_t* n_rows;
+  uint8_t* side;
+  int64_t* rowtime;
+  int64_t* ordinal;
+  int64_t* val;
+  uint8_t* emitted;
+} fw_tjoin_state;
+
+/* open().  Refused before the GPU is touched (FW_ERR_ARG): an unknown join type, lower > upper (the planner's
+ * negative-window-size branch uses no join operator), allowed_lateness < 0, |lower|, |upper| or the lateness >= 2^60,
+ * max_pairs < 0, a bad key kind or key group range.  A failed create returns a handle that carries the message
+ * (fw_tjoin_last_error) and must be destroyed. */
+int fw_tjoin_create(const fw_tjoin_config* cfg, fw_tjoin** out);
+void fw_tjoin_destroy(fw_tjoin* op);
+const char* fw_tjoin_last_error(const fw_tjoin* op);
+/* processElement1 / processElement2 for n tagged rows: side[i] 0 = left, 1 = right; row i gets arrival ordinal (rows
+ * pushed so far) + i; val: one carried int64 per row (NULL = zeros).  Joined rows and the null-padded rows that the
+ * reference emits from processElement are appended to the pending output.  Refused with nothing changed: a row time
+ * < 0 or >= 2^62 (FW_ERR_TIME_RANGE: the reference's behaviour there depends on hash-map iteration order; a row that
+ * is cached has rowtime + relativeSize > operator time >= 0, so the clean-up timer it registers is never <= 0 and is
+ * never read as unset); a key outside the KeyGroupRange (FW_ERR_KEY_GROUP); a side outside {0, 1} (FW_ERR_ARG);
+ * pending rows plus this push's rows above max_pairs (FW_ERR_CAPACITY). */
+int fw_tjoin_push_batch(fw_tjoin* op, const uint8_t* side, const int64_t* key, const int64_t* rowtime,
+                        const int64_t* val, const int32_t* key_hash, int64_t n);
+int fw_tjoin_push_batch_device(fw_tjoin* op, const uint8_t* side, const int64_t* key, const int64_t* rowtime,
+                               const int64_t* val, const int32_t* key_hash, int64_t n);
+/* onTimer for every clean-up timer <= wm, then the watermark the operator forwards: *forwarded_wm = wm -
+ * (max(leftRelativeSize, rightRelativeSize) + allowed_lateness); *n_rows = rows this call emitted (both may be NULL).
+ * A watermark lower than the current one: FW_ERR_ARG. */
+int fw_tjoin_advance_watermark(fw_tjoin* op, int64_t wm, int64_t* n_rows, int64_t* forwarded_wm);
+/* copies up to cap pending output rows to host buffers and removes them; epoch[i] (may be NULL) = the number of
+ * fw_tjoin_advance_watermark calls made before row i was emitted (a timer's rows count their own call as not made) */
+int fw_tjoin_drain(fw_tjoin* op, const fw_tjoin_rows* dst, int64_t* epoch, int64_t cap, int64_t* n);
+/* the pending output rows in HBM (valid until the next call on the handle); they stay pending */
+int fw_tjoin_rows_device(fw_tjoin* op, fw_tjoin_rows* rows, int64_t* n);
+int fw_tjoin_clear_pending(fw_tjoin* op);
+int fw_tjoin_get_stats(fw_tjoin* op, fw_tjoin_stats* out);
+/* snapshotState / initializeState of the keyed state (the two MapState caches, the two timer states).  Snapshot:
+ * *n_keys / *n_rows = the key group's totals; the columns are written when dst is non-NULL and both capacities
+ * suffice.  Restore works into any parallelism; refused with nothing changed: key_group outside the handle's range or
+ * a Long / Integer key that is not in key_group (FW_ERR_KEY_GROUP); a key that occurs twice or already has state
+ * (FW_ERR_STATE); a key with rows in a cache whose timer is 0 (FW_ERR_ARG: left cache rows come with right_timer,
+ * right cache rows with left_timer).  Later pushes are numbered after the largest restored ordinal.  leftExpirationTime,
+ * rightExpirationTime and the watermark are not keyed state: a restored handle starts them at 0, 0 and
+ * Long.MIN_VALUE, as the reference does. */
+int fw_tjoin_snapshot_key_group(fw_tjoin* op, int32_t key_group, const fw_tjoin_state* dst, int64_t cap_keys,
+                                int64_t cap_rows, int64_t* n_keys, int64_t* n_rows);
+int fw_tjoin_restore_key_group(fw_tjoin* op, int32_t key_group, const fw_tjoin_state* src, int64_t n_keys,
+                               int64_t n_rows);
+
 #ifdef __cplusplus
 }
 #endif
