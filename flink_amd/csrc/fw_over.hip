@@ -15,27 +15,11 @@
 //              and range minima, seeded by the key's accumulator (unbounded kinds) -> the keys' new state, the rows
 //              some later frame can still reach back into the store.
 // No kernel walks a key's rows: runs, peer groups and frames cross tiles and workgroups freely.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <string>
 #include <unordered_map>
-#include <unordered_set>
-#include <vector>
 
-#include "../../include/flink_window.h"
-#include "fw_keygroup.h"
+#include "fw_table.h"
 
 namespace {
-
-constexpr int64_t LMAX = INT64_MAX;
-constexpr int64_t LMIN = INT64_MIN;
-#include "fw_jmath.h"
 
 constexpr int OV_THREADS = 512, OV_ITEMS = 8, OV_TILE = OV_THREADS * OV_ITEMS;  // rows per scan workgroup
 constexpr int OV_BLOCK = 64, OV_LEVELS = 6;  // range minima: spans 2^1 .. 2^6 per row, then one table over 64-row blocks
@@ -62,18 +46,10 @@ struct OCtr {
   int32_t pad;
 };
 
-struct OMap {
-  int64_t* mkey;
-  uint32_t* mstate;  // 0 empty, 1 being published, 2 taken
-  uint32_t* mslot;
-  uint32_t mask;
-  // per key slot
-  int64_t* skey;
-  int32_t* skg;
+struct OMap : KeyMap {  // per key slot, besides the key and its key group
   int64_t* slast;    // lastTriggeringTs (bounded kinds), 0 = fresh
   int64_t* sacc;     // [slot * accw] the unbounded kinds' accumulator Row
   uint32_t* stouch;  // the watermark call that last found a row of the key to fire
-  int32_t max_keys;
 };
 
 struct ORowsD {  // the row store, or a watermark's gathered rows: columns of `cap` rows
@@ -89,84 +65,6 @@ __host__ __device__ inline bool ov_float(int t) { return t == FW_VAL_F64 || t ==
 __host__ __device__ inline int64_t ov_narrow(int t, int64_t v) {
   return t == FW_VAL_I32 ? (int64_t)(int32_t)v : t == FW_VAL_I16 ? (int64_t)(int16_t)v
        : t == FW_VAL_I8 ? (int64_t)(int8_t)v : v;
-}
-
-// ---------------------------------------------------------------- key map
-__device__ __forceinline__ uint32_t ov_home(const OMap& m, int64_t key) {
-  return (uint32_t)fmix64((uint64_t)key ^ 0x9E3779B97F4A7C15ull) & m.mask;
-}
-// the key's slot, or -1 (lookup only)
-__device__ __forceinline__ int32_t ov_find(const OMap& m, int64_t key) {
-  uint32_t s = ov_home(m, key);
-  for (uint32_t probes = 0; probes <= m.mask; probes++) {
-    const uint32_t cur = m.mstate[s];
-    if (cur == 0) return -1;
-    if (m.mkey[s] == key) return (int32_t)m.mslot[s];
-    s = (s + 1) & m.mask;
-  }
-  return -1;
-}
-// find or claim (the pattern of the count windows' key map): a claiming lane publishes key and slot before the state
-template <class KG>
-__device__ __forceinline__ int32_t ov_claim(const OMap& m, OCtr* ctr, int64_t key, KG kg_of) {
-  uint32_t s = ov_home(m, key);
-  for (uint32_t probes = 0; probes <= m.mask;) {
-    const uint32_t cur = __hip_atomic_load(&m.mstate[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __atomic_signal_fence(__ATOMIC_ACQUIRE);
-    if (cur == 2) {
-      if (__hip_atomic_load(&m.mkey[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == key) {
-        const uint32_t slot = __hip_atomic_load(&m.mslot[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (slot >= (uint32_t)m.max_keys) break;
-        return (int32_t)slot;
-      }
-      s = (s + 1) & m.mask;
-      probes++;
-      continue;
-    }
-    if (cur == 1) continue;  // being published by another lane: re-read
-    if (atomicCAS(&m.mstate[s], 0u, 1u) == 0u) {
-      const int32_t slot = atomicAdd(&ctr->nslots, 1);
-      __hip_atomic_store(&m.mkey[s], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&m.mslot[s], (uint32_t)slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (slot < m.max_keys) {
-        m.skey[slot] = key;
-        m.skg[slot] = kg_of();
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&m.mstate[s], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (slot >= m.max_keys) {
-        atomicAdd(&ctr->map_full, 1ull);
-        return -1;
-      }
-      return slot;
-    }
-  }
-  atomicAdd(&ctr->map_full, 1ull);
-  return -1;
-}
-// rebuild of a grown map from the slots' keys (no lookups run beside it)
-__global__ __launch_bounds__(256) void k_ov_rehash(OMap m, int32_t nslots) {
-  const int32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-  if (slot >= nslots) return;
-  const int64_t key = m.skey[slot];
-  uint32_t s = ov_home(m, key);
-  for (uint32_t probes = 0; probes <= m.mask; probes++) {
-    if (atomicCAS(&m.mstate[s], 0u, 2u) == 0u) {
-      m.mkey[s] = key;
-      m.mslot[s] = (uint32_t)slot;
-      return;
-    }
-    s = (s + 1) & m.mask;
-  }
-}
-
-__device__ __forceinline__ unsigned long long wave_count(bool p) { return (unsigned long long)__popcll(__ballot(p)); }
-__device__ __forceinline__ int64_t wave_min64(int64_t v) {
-  for (int d = 32; d >= 1; d >>= 1) {
-    const int64_t o = __shfl_xor(v, d, 64);
-    v = o < v ? o : v;
-  }
-  return v;
 }
 
 // ---------------------------------------------------------------- push
@@ -200,7 +98,7 @@ __global__ __launch_bounds__(256) void k_ov_slots(OCfg c, OMap m, int64_t wm, co
     const int64_t k = key[i];
     int32_t slot = -1;
     if (ov_bounded(c) ? t > 0 : t > wm) {
-      slot = ov_claim(m, ctr, k, [&] { return key_group(key_hash_of(c.key_kind, k, kh, i), c.max_par); });
+      slot = keymap_claim(m, &ctr->nslots, &ctr->map_full, k, [&] { return key_group(key_hash_of(c.key_kind, k, kh, i), c.max_par); });
       kept = slot >= 0 && (!ov_bounded(c) || t > m.slast[slot]);
     }
     late = !kept;
@@ -815,7 +713,7 @@ __global__ __launch_bounds__(256) void k_ov_restore_keys(OCfg c, OMap m, OCtr* c
                                                          int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int32_t slot = ov_claim(m, ctr, key[i], [&] { return kg; });
+  const int32_t slot = keymap_claim(m, &ctr->nslots, &ctr->map_full, key[i], [&] { return kg; });
   if (slot < 0) return;
   m.slast[slot] = ov_bounded(c) ? last[i] : 0;
   const int w = ov_accw(c);
@@ -829,26 +727,23 @@ __global__ __launch_bounds__(256) void k_ov_restore_rows(OCfg c, OMap m, ORowsD 
   if (i >= n) return;
   const int64_t d = base + i;
   if (d >= st.cap) return;
-  st.slot[d] = (uint32_t)ov_find(m, key[i]);
+  st.slot[d] = (uint32_t)keymap_find(m, key[i]);
   st.ts[d] = ts[i];
   st.ord[d] = ord[i];
   st.nul[d] = nul[i];
   for (int j = 0; j < c.nc; j++) st.cols[(int64_t)j * st.cap + d] = cols[i * c.nc + j];
 }
 
-struct Buf {  // scratch that only grows; contents are not kept
-  void* p = nullptr;
-  size_t cap = 0;
+struct OOut {  // the pending output rows: columns of the handle's `ocap` rows (val: ns words a row)
+  int64_t *key, *ts, *ord, *val;
+  uint32_t* nul;
 };
 
 }  // namespace
 
-struct fw_over {
+struct fw_over : TableHandle {  // (oseg's epochs: the watermark calls)
   fw_over_config cfg{};
   OCfg c{};
-  std::string err;
-  bool ready = false;
-  hipStream_t stream = nullptr;
   OMap map{};
   OCtr* ctr = nullptr;       // device
   OCtr* hctr = nullptr;      // pinned host copy
@@ -861,13 +756,9 @@ struct fw_over {
   int64_t kept_total = 0, late_total = 0, fired_total = 0;
   uint32_t epoch = 0;        // watermark calls that did work (stouch's stamp)
   int64_t wm_calls = 0;
-  // pending output
-  int64_t *okey = nullptr, *ots = nullptr, *oord = nullptr, *oval = nullptr;
-  uint32_t* onul = nullptr;
-  int64_t ocap = 0, n_out = 0;
-  std::vector<std::pair<int64_t, int64_t>> oseg;  // (watermark call, rows)
+  OOut out{};
   uint32_t used_cols = 0, min_cols = 0, max_cols = 0;
-  Buf b_stage[5], b_pslot, b_pkeep, b_ppos, b_tmp, b_sel, b_pos, b_sk[2], b_sv[2], b_k2[2];
+  Buf b_stage[5], b_pslot, b_pkeep, b_ppos, b_sel, b_pos, b_sk[2], b_sv[2], b_k2[2];
   Buf b_g[5], b_flo, b_fhi, b_fire, b_keep, b_opos, b_kpos, b_thead;
   Buf b_pnn[8], b_plo[8], b_phi[8], b_tagg[8], b_carry[8];
   Buf b_rbase[16], b_rst[16], b_rbt[16];
@@ -875,203 +766,25 @@ struct fw_over {
 
 namespace {
 
-int set_err(fw_over* op, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  op->err = buf;
-  return code;
+// the column sets: the row store (cols: a column-major matrix, one plane per column), a key slot's state, the output
+auto row_cols(const fw_over* op) {
+  return [nc = op->c.nc](ORowsD& r) { return Cols{col(r.slot), col(r.ts), col(r.ord), col(r.cols, 8, nc), col(r.nul)}; };
 }
-#define OHIP(op, expr)                                                                                     \
-  do {                                                                                                     \
-    hipError_t _e = (expr);                                                                                \
-    if (_e != hipSuccess) return set_err(op, FW_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
-
-inline unsigned grid_of(int64_t n, int t = 256) { return (unsigned)std::max<int64_t>(1, (n + t - 1) / t); }
-
-int ensure(fw_over* op, Buf& b, size_t bytes) {
-  if (bytes <= b.cap) return FW_OK;
-  size_t want = std::max(bytes, b.cap + b.cap / 2);
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  if (hipMalloc(&b.p, want) != hipSuccess) {
-    (void)hipGetLastError();
-    b.p = nullptr;
-    return set_err(op, FW_ERR_CAPACITY, "cannot allocate %zu bytes of scratch", want);
-  }
-  b.cap = want;
-  return FW_OK;
+auto slot_cols(const fw_over* op) {  // (besides the key map's own skey, skg)
+  return [w = (size_t)8 * ov_accw(op->c)](OMap& m) { return Cols{col(m.slast, 8, 1, 0), col(m.sacc, w, 1, 0), col(m.stouch, 4, 1, 0)}; };
+}
+auto out_cols(const fw_over* op) {
+  return [w = (size_t)8 * op->c.ns](OOut& o) { return Cols{col(o.key), col(o.ts), col(o.ord), col(o.val, w), col(o.nul)}; };
 }
 
-void free_rows(ORowsD& r) {
-  (void)hipFree(r.slot);
-  (void)hipFree(r.ts);
-  (void)hipFree(r.ord);
-  (void)hipFree(r.cols);
-  (void)hipFree(r.nul);
-  r = ORowsD{};
-}
-int alloc_rows(fw_over* op, ORowsD& r, int64_t cap) {
-  r = ORowsD{};
-  r.cap = cap;
-  const size_t n = (size_t)cap;
-  if (hipMalloc(&r.slot, n * 4) != hipSuccess || hipMalloc(&r.ts, n * 8) != hipSuccess ||
-      hipMalloc(&r.ord, n * 8) != hipSuccess || hipMalloc(&r.cols, n * 8 * op->c.nc) != hipSuccess ||
-      hipMalloc(&r.nul, n) != hipSuccess) {
-    (void)hipGetLastError();
-    free_rows(r);
-    return set_err(op, FW_ERR_CAPACITY, "cannot allocate a row store of %lld rows", (long long)cap);
-  }
-  return FW_OK;
-}
-// both store buffers to at least `need` rows; the live one keeps its rows
 int grow_store(fw_over* op, int64_t need) {
-  if (need <= op->store[0].cap) return FW_OK;
-  if (need >= (int64_t(1) << 31)) return set_err(op, FW_ERR_CAPACITY, "the row store would exceed 2^31 rows");
-  int64_t cap = std::max<int64_t>(op->store[0].cap, 1024);
-  while (cap < need) cap *= 2;
-  ORowsD a, b;
-  int rc = alloc_rows(op, a, cap);
-  if (rc) return rc;
-  rc = alloc_rows(op, b, cap);
-  if (rc) {
-    free_rows(a);
-    return rc;
-  }
-  const ORowsD& o = op->store[op->cur];
-  const size_t n = (size_t)op->n_store;
-  if (n) {
-    OHIP(op, hipMemcpyAsync(a.slot, o.slot, n * 4, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(a.ts, o.ts, n * 8, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(a.ord, o.ord, n * 8, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(a.nul, o.nul, n, hipMemcpyDeviceToDevice, op->stream));
-    for (int j = 0; j < op->c.nc; j++)
-      OHIP(op, hipMemcpyAsync(a.cols + (int64_t)j * cap, o.cols + (int64_t)j * o.cap, n * 8, hipMemcpyDeviceToDevice,
-                              op->stream));
-    OHIP(op, hipStreamSynchronize(op->stream));
-  }
-  free_rows(op->store[0]);
-  free_rows(op->store[1]);
-  op->store[0] = a;
-  op->store[1] = b;
-  op->cur = 0;
-  return FW_OK;
+  return grow_store(op, op->store, op->cur, op->n_store, need, row_cols(op));
 }
-
-void free_map(OMap& m) {
-  (void)hipFree(m.mkey);
-  (void)hipFree(m.mstate);
-  (void)hipFree(m.mslot);
-  (void)hipFree(m.skey);
-  (void)hipFree(m.skg);
-  (void)hipFree(m.slast);
-  (void)hipFree(m.sacc);
-  (void)hipFree(m.stouch);
-  m = OMap{};
-}
-// a key map for at least `keys` keys (load <= 1/2); the slots' state moves over and the map is rebuilt from their keys
 int grow_map(fw_over* op, int64_t keys) {
-  if (keys <= op->map.max_keys) return FW_OK;
-  if (keys >= (int64_t(1) << 30)) return set_err(op, FW_ERR_CAPACITY, "the key map would exceed 2^30 keys");
-  int64_t mk = std::max<int64_t>(op->map.max_keys, 1024);
-  while (mk < keys) mk *= 2;
-  const int64_t cap = mk * 2;
-  const int w = ov_accw(op->c);
-  OMap n{};
-  n.mask = (uint32_t)(cap - 1);
-  n.max_keys = (int32_t)mk;
-  if (hipMalloc(&n.mkey, cap * 8) != hipSuccess || hipMalloc(&n.mstate, cap * 4) != hipSuccess ||
-      hipMalloc(&n.mslot, cap * 4) != hipSuccess || hipMalloc(&n.skey, mk * 8) != hipSuccess ||
-      hipMalloc(&n.skg, mk * 4) != hipSuccess || hipMalloc(&n.slast, mk * 8) != hipSuccess ||
-      hipMalloc(&n.sacc, mk * 8 * w) != hipSuccess || hipMalloc(&n.stouch, mk * 4) != hipSuccess) {
-    (void)hipGetLastError();
-    free_map(n);
-    return set_err(op, FW_ERR_CAPACITY, "cannot allocate a key map of %lld keys", (long long)mk);
-  }
-  OHIP(op, hipMemsetAsync(n.mstate, 0, cap * 4, op->stream));
-  OHIP(op, hipMemsetAsync(n.slast, 0, mk * 8, op->stream));
-  OHIP(op, hipMemsetAsync(n.sacc, 0, mk * 8 * w, op->stream));
-  OHIP(op, hipMemsetAsync(n.stouch, 0, mk * 4, op->stream));
-  const int64_t ns = op->nslots;
-  if (ns) {
-    const OMap& o = op->map;
-    OHIP(op, hipMemcpyAsync(n.skey, o.skey, ns * 8, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(n.skg, o.skg, ns * 4, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(n.slast, o.slast, ns * 8, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(n.sacc, o.sacc, ns * 8 * w, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(n.stouch, o.stouch, ns * 4, hipMemcpyDeviceToDevice, op->stream));
-    hipLaunchKernelGGL(k_ov_rehash, dim3(grid_of(ns)), dim3(256), 0, op->stream, n, (int32_t)ns);
-  }
-  OHIP(op, hipStreamSynchronize(op->stream));
-  free_map(op->map);
-  op->map = n;
-  return FW_OK;
+  return grow_map(op, op->map, op->nslots, keys, 30, slot_cols(op));
 }
-
 int grow_out(fw_over* op, int64_t need) {
-  if (need <= op->ocap) return FW_OK;
-  int64_t cap = std::max<int64_t>(op->ocap, 1024);
-  while (cap < need) cap *= 2;
-  int64_t *k = nullptr, *t = nullptr, *o = nullptr, *v = nullptr;
-  uint32_t* nm = nullptr;
-  const int ns = op->c.ns;
-  if (hipMalloc(&k, cap * 8) != hipSuccess || hipMalloc(&t, cap * 8) != hipSuccess ||
-      hipMalloc(&o, cap * 8) != hipSuccess || hipMalloc(&v, cap * 8 * ns) != hipSuccess ||
-      hipMalloc(&nm, cap * 4) != hipSuccess) {
-    (void)hipGetLastError();
-    (void)hipFree(k);
-    (void)hipFree(t);
-    (void)hipFree(o);
-    (void)hipFree(v);
-    (void)hipFree(nm);
-    return set_err(op, FW_ERR_CAPACITY, "cannot allocate an output buffer of %lld rows", (long long)cap);
-  }
-  const size_t n = (size_t)op->n_out;
-  if (n) {
-    OHIP(op, hipMemcpyAsync(k, op->okey, n * 8, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(t, op->ots, n * 8, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(o, op->oord, n * 8, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(v, op->oval, n * 8 * ns, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipMemcpyAsync(nm, op->onul, n * 4, hipMemcpyDeviceToDevice, op->stream));
-    OHIP(op, hipStreamSynchronize(op->stream));
-  }
-  (void)hipFree(op->okey);
-  (void)hipFree(op->ots);
-  (void)hipFree(op->oord);
-  (void)hipFree(op->oval);
-  (void)hipFree(op->onul);
-  op->okey = k;
-  op->ots = t;
-  op->oord = o;
-  op->oval = v;
-  op->onul = nm;
-  op->ocap = cap;
-  return FW_OK;
-}
-
-// the device counters to the host (settles the stream)
-int read_ctr(fw_over* op) {
-  OHIP(op, hipMemcpyAsync(op->hctr, op->ctr, sizeof(OCtr), hipMemcpyDeviceToHost, op->stream));
-  OHIP(op, hipStreamSynchronize(op->stream));
-  return FW_OK;
-}
-int write_ctr(fw_over* op) {
-  OHIP(op, hipMemcpyAsync(op->ctr, op->hctr, sizeof(OCtr), hipMemcpyHostToDevice, op->stream));
-  OHIP(op, hipStreamSynchronize(op->stream));
-  return FW_OK;
-}
-
-int excl_scan(fw_over* op, const uint32_t* in, uint32_t* out, int64_t n) {
-  size_t bytes = 0;
-  OHIP(op, rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), op->stream));
-  int rc = ensure(op, op->b_tmp, bytes);
-  if (rc) return rc;
-  OHIP(op, rocprim::exclusive_scan(op->b_tmp.p, bytes, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), op->stream));
-  return FW_OK;
+  return cols_grow(op, op->out, op->ocap, need, op->n_out, out_cols(op), "cannot allocate an output buffer of %lld rows");
 }
 
 template <bool F64>
@@ -1110,7 +823,7 @@ int do_push(fw_over* op, const int64_t* key, const int64_t* ts, const int64_t* c
   hipLaunchKernelGGL(k_ov_append, dim3(grid_of(n)), dim3(256), 0, op->stream, op->c, op->store[op->cur], op->n_store, ts,
                      cols, nulls, n, op->ord_base, pslot, pkeep, ppos);
   if ((rc = read_ctr(op))) return rc;
-  OHIP(op, hipGetLastError());
+  TB_HIP(op, hipGetLastError());
   if (op->hctr->map_full) return set_err(op, FW_ERR_STATE, "the key map overflowed");
   const int64_t kept = (int64_t)op->hctr->kept - op->kept_total;
   op->kept_total = (int64_t)op->hctr->kept;
@@ -1144,12 +857,12 @@ int do_watermark(fw_over* op, int64_t wm, int64_t* n_rows) {
   if ((rc = excl_scan(op, sel, pos, n))) return rc;
   hipLaunchKernelGGL(k_ov_total, dim3(1), dim3(1), 0, op->stream, sel, pos, n, op->tot);
   op->hctr->due_rest = LMAX;  // (hctr mirrors the device after the last read_ctr)
-  OHIP(op, hipMemcpyAsync(&op->ctr->due_rest, &op->hctr->due_rest, 8, hipMemcpyHostToDevice, op->stream));
+  TB_HIP(op, hipMemcpyAsync(&op->ctr->due_rest, &op->hctr->due_rest, 8, hipMemcpyHostToDevice, op->stream));
   hipLaunchKernelGGL(k_ov_split, dim3(grid_of(n)), dim3(256), 0, op->stream, c, op->map, wm, st, other, n, sel, pos,
                      (uint64_t*)op->b_sk[0].p, (uint32_t*)op->b_sv[0].p, op->ctr);
   unsigned long long htot[2] = {0, 0};
-  OHIP(op, hipMemcpyAsync(htot, op->tot, 8, hipMemcpyDeviceToHost, op->stream));
-  OHIP(op, hipStreamSynchronize(op->stream));
+  TB_HIP(op, hipMemcpyAsync(htot, op->tot, 8, hipMemcpyDeviceToHost, op->stream));
+  TB_HIP(op, hipStreamSynchronize(op->stream));
   const int64_t m = (int64_t)htot[0], rest = n - m;
   if (m == 0) {  // (next_due was stale: rows below it were all retained ones of untouched keys)
     op->cur ^= 1;
@@ -1159,28 +872,19 @@ int do_watermark(fw_over* op, int64_t wm, int64_t* n_rows) {
   }
   // stable sort by row time, then by key: a key's run in (row time, arrival) order
   {
-    rocprim::double_buffer<uint64_t> ks((uint64_t*)op->b_sk[0].p, (uint64_t*)op->b_sk[1].p);
-    rocprim::double_buffer<uint32_t> vs((uint32_t*)op->b_sv[0].p, (uint32_t*)op->b_sv[1].p);
-    size_t bytes = 0;
-    OHIP(op, rocprim::radix_sort_pairs(nullptr, bytes, ks, vs, (size_t)m, 0, 64, op->stream));
-    if ((rc = ensure(op, op->b_tmp, bytes))) return rc;
-    OHIP(op, rocprim::radix_sort_pairs(op->b_tmp.p, bytes, ks, vs, (size_t)m, 0, 64, op->stream));
-    const uint32_t* sv1 = vs.current();
-    uint32_t* other_v = sv1 == (uint32_t*)op->b_sv[0].p ? (uint32_t*)op->b_sv[1].p : (uint32_t*)op->b_sv[0].p;
-    hipLaunchKernelGGL(k_ov_slot_keys, dim3(grid_of(m)), dim3(256), 0, op->stream, op->map, st, sv1, m,
-                       (uint64_t*)op->b_k2[0].p);
-    rocprim::double_buffer<uint64_t> k2((uint64_t*)op->b_k2[0].p, (uint64_t*)op->b_k2[1].p);
-    rocprim::double_buffer<uint32_t> v2(const_cast<uint32_t*>(sv1), other_v);
-    OHIP(op, rocprim::radix_sort_pairs(nullptr, bytes, k2, v2, (size_t)m, 0, 64, op->stream));
-    if ((rc = ensure(op, op->b_tmp, bytes))) return rc;
-    OHIP(op, rocprim::radix_sort_pairs(op->b_tmp.p, bytes, k2, v2, (size_t)m, 0, 64, op->stream));
+    uint64_t *sk0 = (uint64_t*)op->b_sk[0].p, *sk1 = (uint64_t*)op->b_sk[1].p;
+    uint64_t *k20 = (uint64_t*)op->b_k2[0].p, *k21 = (uint64_t*)op->b_k2[1].p;
+    uint32_t *sv0 = (uint32_t*)op->b_sv[0].p, *sv1 = (uint32_t*)op->b_sv[1].p;
+    if ((rc = sort_pairs<uint64_t>(op, sk0, sk1, sv0, sv1, m, 64u))) return rc;
+    hipLaunchKernelGGL(k_ov_slot_keys, dim3(grid_of(m)), dim3(256), 0, op->stream, op->map, st, (const uint32_t*)sv1, m, k20);
+    if ((rc = sort_pairs<uint64_t>(op, k20, k21, sv1, sv0, m, 64u))) return rc;  // (sv0: the rows' final order)
     // the gathered rows
     const size_t sz[5] = {(size_t)m * 4, (size_t)m * 8, (size_t)m * 8, (size_t)m * 8 * c.nc, (size_t)m};
     for (int q = 0; q < 5; q++)
       if ((rc = ensure(op, op->b_g[q], sz[q]))) return rc;
     ORowsD g{(uint32_t*)op->b_g[0].p, (int64_t*)op->b_g[1].p, (int64_t*)op->b_g[2].p, (int64_t*)op->b_g[3].p,
              (uint8_t*)op->b_g[4].p, m};
-    hipLaunchKernelGGL(k_ov_gather, dim3(grid_of(m)), dim3(256), 0, op->stream, c, st, g, v2.current(), m);
+    hipLaunchKernelGGL(k_ov_gather, dim3(grid_of(m)), dim3(256), 0, op->stream, c, st, g, (const uint32_t*)sv0, m);
   }
   ORowsD g{(uint32_t*)op->b_g[0].p, (int64_t*)op->b_g[1].p, (int64_t*)op->b_g[2].p, (int64_t*)op->b_g[3].p,
            (uint8_t*)op->b_g[4].p, m};
@@ -1236,26 +940,26 @@ int do_watermark(fw_over* op, int64_t wm, int64_t* n_rows) {
       (is_max ? sc.mx[j] : sc.mn[j]) = r;
     }
   }
-  OHIP(op, hipMemcpyAsync(htot, op->tot, 16, hipMemcpyDeviceToHost, op->stream));
-  OHIP(op, hipStreamSynchronize(op->stream));
+  TB_HIP(op, hipMemcpyAsync(htot, op->tot, 16, hipMemcpyDeviceToHost, op->stream));
+  TB_HIP(op, hipStreamSynchronize(op->stream));
   const int64_t nfire = (int64_t)htot[0], nkeep = (int64_t)htot[1];
   if ((rc = grow_out(op, op->n_out + nfire))) return rc;  // the row buffer, from the exact count
   hipLaunchKernelGGL(k_ov_eval, dim3(grid_of(m)), dim3(256), 0, op->stream, c, op->map, sc, g, m, flo, fhi, fire, opos,
-                     op->n_out, op->ocap, op->okey, op->ots, op->oord, op->oval, op->onul);
+                     op->n_out, op->ocap, op->out.key, op->out.ts, op->out.ord, op->out.val, op->out.nul);
   hipLaunchKernelGGL(k_ov_state, dim3(grid_of(m)), dim3(256), 0, op->stream, c, op->map, sc, g, m, flo, fire, op->used_cols);
   hipLaunchKernelGGL(k_ov_retain, dim3(grid_of(m)), dim3(256), 0, op->stream, c, g, other, m, rest, keep, kpos);
   if ((rc = read_ctr(op))) return rc;
-  OHIP(op, hipGetLastError());
+  TB_HIP(op, hipGetLastError());
   op->cur ^= 1;
   op->n_store = rest + nkeep;
   op->pending -= nfire;
   op->next_due = op->hctr->due_rest;
   op->hctr->next_due = op->next_due;
-  OHIP(op, hipMemcpyAsync(&op->ctr->next_due, &op->hctr->next_due, 8, hipMemcpyHostToDevice, op->stream));
-  OHIP(op, hipStreamSynchronize(op->stream));
+  TB_HIP(op, hipMemcpyAsync(&op->ctr->next_due, &op->hctr->next_due, 8, hipMemcpyHostToDevice, op->stream));
+  TB_HIP(op, hipStreamSynchronize(op->stream));
   op->n_out += nfire;
   op->fired_total += nfire;
-  if (nfire) op->oseg.emplace_back(call, nfire);
+  append_segment(op, call, nfire);
   if (n_rows) *n_rows = nfire;
   return FW_OK;
 }
@@ -1269,6 +973,7 @@ int fw_over_create(const fw_over_config* cfg, fw_over** out) {
   *out = nullptr;
   fw_over* op = new fw_over();
   op->cfg = *cfg;
+  op->device = cfg->device;
   const fw_over_config& c = *cfg;
   auto fail = [&](int code, const char* msg) {  // as fw_create: the handle carries the message; destroy it
     op->err = msg;
@@ -1327,11 +1032,11 @@ int fw_over_create(const fw_over_config* cfg, fw_over** out) {
     (void)hipGetLastError();
     return set_err(op, FW_ERR_HIP, "device %d is not available (%d devices)", c.device, ndev);
   }
-  OHIP(op, hipSetDevice(c.device));
-  OHIP(op, hipStreamCreateWithFlags(&op->stream, hipStreamNonBlocking));
-  OHIP(op, hipMalloc(&op->ctr, sizeof(OCtr)));
-  OHIP(op, hipMalloc(&op->tot, 16));
-  OHIP(op, hipHostMalloc(&op->hctr, sizeof(OCtr)));
+  TB_HIP(op, hipSetDevice(c.device));
+  TB_HIP(op, hipStreamCreateWithFlags(&op->stream, hipStreamNonBlocking));
+  TB_HIP(op, hipMalloc(&op->ctr, sizeof(OCtr)));
+  TB_HIP(op, hipMalloc(&op->tot, 16));
+  TB_HIP(op, hipHostMalloc(&op->hctr, sizeof(OCtr)));
   memset(op->hctr, 0, sizeof(OCtr));
   op->hctr->next_due = LMAX;
   op->hctr->due_rest = LMAX;
@@ -1347,39 +1052,14 @@ int fw_over_create(const fw_over_config* cfg, fw_over** out) {
 void fw_over_destroy(fw_over* op) {
   if (!op) return;
   if (op->stream) {
-    (void)hipSetDevice(op->cfg.device);
+    (void)hipSetDevice(op->device);
     (void)hipStreamSynchronize(op->stream);
-    free_map(op->map);
-    free_rows(op->store[0]);
-    free_rows(op->store[1]);
+    free_map(op->map, slot_cols(op));
+    for (ORowsD& r : op->store) cols_free(row_cols(op)(r));
+    cols_free(out_cols(op)(op->out));
     (void)hipFree(op->ctr);
     (void)hipFree(op->tot);
     (void)hipHostFree(op->hctr);
-    (void)hipFree(op->okey);
-    (void)hipFree(op->ots);
-    (void)hipFree(op->oord);
-    (void)hipFree(op->oval);
-    (void)hipFree(op->onul);
-    Buf* all[] = {&op->b_pslot, &op->b_pkeep, &op->b_ppos, &op->b_tmp, &op->b_sel, &op->b_pos, &op->b_sk[0], &op->b_sk[1],
-                  &op->b_sv[0], &op->b_sv[1], &op->b_k2[0], &op->b_k2[1], &op->b_flo, &op->b_fhi, &op->b_fire,
-                  &op->b_keep, &op->b_opos, &op->b_kpos, &op->b_thead};
-    for (Buf* b : all) (void)hipFree(b->p);
-    for (int q = 0; q < 5; q++) {
-      (void)hipFree(op->b_stage[q].p);
-      (void)hipFree(op->b_g[q].p);
-    }
-    for (int q = 0; q < 8; q++) {
-      (void)hipFree(op->b_pnn[q].p);
-      (void)hipFree(op->b_plo[q].p);
-      (void)hipFree(op->b_phi[q].p);
-      (void)hipFree(op->b_tagg[q].p);
-      (void)hipFree(op->b_carry[q].p);
-    }
-    for (int q = 0; q < 16; q++) {
-      (void)hipFree(op->b_rbase[q].p);
-      (void)hipFree(op->b_rst[q].p);
-      (void)hipFree(op->b_rbt[q].p);
-    }
     (void)hipStreamDestroy(op->stream);
   }
   delete op;
@@ -1389,103 +1069,64 @@ const char* fw_over_last_error(const fw_over* op) { return op ? op->err.c_str() 
 
 int fw_over_push_batch_device(fw_over* op, const int64_t* key, const int64_t* rowtime, const int64_t* cols,
                               const uint8_t* nulls, const int32_t* key_hash, int64_t n) {
-  if (!op) return FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  if (n < 0 || (n > 0 && (!key || !rowtime || !cols))) return set_err(op, FW_ERR_ARG, "null column");
-  if (op->c.key_kind == FW_KEY_HASHED && n > 0 && !key_hash)
-    return set_err(op, FW_ERR_ARG, "key_hash required for FW_KEY_HASHED");
-  OHIP(op, hipSetDevice(op->cfg.device));
+  int rc;
+  if ((rc = enter_push(op, !key || !rowtime || !cols, key_hash, n)) || (rc = on_device(op))) return rc;
   return do_push(op, key, rowtime, cols, nulls, key_hash, n);
 }
 
 int fw_over_push_batch(fw_over* op, const int64_t* key, const int64_t* rowtime, const int64_t* cols,
                        const uint8_t* nulls, const int32_t* key_hash, int64_t n) {
-  if (!op) return FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  if (n < 0 || (n > 0 && (!key || !rowtime || !cols))) return set_err(op, FW_ERR_ARG, "null column");
-  if (op->c.key_kind == FW_KEY_HASHED && n > 0 && !key_hash)
-    return set_err(op, FW_ERR_ARG, "key_hash required for FW_KEY_HASHED");
+  int rc;
+  if ((rc = enter_push(op, !key || !rowtime || !cols, key_hash, n))) return rc;
   if (n == 0) return FW_OK;
   for (int64_t i = 0; i < n; i++)
     if (rowtime[i] == LMIN)
       return set_err(op, FW_ERR_NO_TIMESTAMP, "row %lld has a Long.MIN_VALUE row time; the push was refused", (long long)i);
-  OHIP(op, hipSetDevice(op->cfg.device));
+  if ((rc = on_device(op))) return rc;
   const size_t sz[5] = {(size_t)n * 8, (size_t)n * 8, (size_t)n * 8 * op->c.nc, (size_t)n, (size_t)n * 4};
   const void* src[5] = {key, rowtime, cols, nulls, key_hash};
-  int rc;
   for (int q = 0; q < 5; q++) {
     if (!src[q]) continue;
     if ((rc = ensure(op, op->b_stage[q], sz[q]))) return rc;
-    OHIP(op, hipMemcpyAsync(op->b_stage[q].p, src[q], sz[q], hipMemcpyHostToDevice, op->stream));
+    TB_HIP(op, hipMemcpyAsync(op->b_stage[q].p, src[q], sz[q], hipMemcpyHostToDevice, op->stream));
   }
-  OHIP(op, hipStreamSynchronize(op->stream));
+  TB_HIP(op, hipStreamSynchronize(op->stream));
   return do_push(op, (const int64_t*)op->b_stage[0].p, (const int64_t*)op->b_stage[1].p, (const int64_t*)op->b_stage[2].p,
                  nulls ? (const uint8_t*)op->b_stage[3].p : nullptr, key_hash ? (const int32_t*)op->b_stage[4].p : nullptr, n);
 }
 
 int fw_over_advance_watermark(fw_over* op, int64_t wm, int64_t* n_rows) {
-  if (!op) return FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
+  int rc;
+  if ((rc = enter(op))) return rc;
   if (wm < op->wm) return set_err(op, FW_ERR_ARG, "watermark %lld is lower than the current %lld", (long long)wm, (long long)op->wm);
-  OHIP(op, hipSetDevice(op->cfg.device));
+  if ((rc = on_device(op))) return rc;
   return do_watermark(op, wm, n_rows);
 }
 
 int fw_over_drain(fw_over* op, const fw_over_rows* dst, int64_t* epoch, int64_t cap, int64_t* n) {
-  if (!op || !dst || !n || cap < 0) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  OHIP(op, hipSetDevice(op->cfg.device));
-  const int64_t k = std::min(cap, op->n_out);
-  *n = k;
-  if (k == 0) return FW_OK;
-  const int ns = op->c.ns;
-  if (dst->key) OHIP(op, hipMemcpyAsync(dst->key, op->okey, k * 8, hipMemcpyDeviceToHost, op->stream));
-  if (dst->rowtime) OHIP(op, hipMemcpyAsync(dst->rowtime, op->ots, k * 8, hipMemcpyDeviceToHost, op->stream));
-  if (dst->ordinal) OHIP(op, hipMemcpyAsync(dst->ordinal, op->oord, k * 8, hipMemcpyDeviceToHost, op->stream));
-  if (dst->values) OHIP(op, hipMemcpyAsync(dst->values, op->oval, k * 8 * ns, hipMemcpyDeviceToHost, op->stream));
-  if (dst->null_mask) OHIP(op, hipMemcpyAsync(dst->null_mask, op->onul, k * 4, hipMemcpyDeviceToHost, op->stream));
-  const int64_t left = op->n_out - k;
-  OHIP(op, hipStreamSynchronize(op->stream));
-  if (left) {  // (a partial drain: the rest moves to the front through a bounce buffer)
-    int rc;
-    const size_t big = (size_t)left * 8 * std::max(ns, 1);
-    if ((rc = ensure(op, op->b_tmp, big))) return rc;
-    struct { void* p; size_t w; } col[5] = {{op->okey, 8}, {op->ots, 8}, {op->oord, 8}, {op->oval, (size_t)8 * ns}, {op->onul, 4}};
-    for (auto& cc : col) {
-      OHIP(op, hipMemcpyAsync(op->b_tmp.p, (char*)cc.p + (size_t)k * cc.w, (size_t)left * cc.w, hipMemcpyDeviceToDevice, op->stream));
-      OHIP(op, hipMemcpyAsync(cc.p, op->b_tmp.p, (size_t)left * cc.w, hipMemcpyDeviceToDevice, op->stream));
-    }
-    OHIP(op, hipStreamSynchronize(op->stream));
-  }
-  int64_t w = 0;
-  while (w < k && !op->oseg.empty()) {
-    auto& s = op->oseg.front();
-    const int64_t take = std::min(s.second, k - w);
-    if (epoch) std::fill(epoch + w, epoch + w + take, s.first);
-    w += take;
-    s.second -= take;
-    if (s.second == 0) op->oseg.erase(op->oseg.begin());
-  }
-  op->n_out = left;
-  return FW_OK;
+  int rc;
+  if ((rc = enter(op, !dst || !n || cap < 0)) || (rc = on_device(op))) return rc;
+  const OOut& o = op->out;
+  return drain_pending(op, {{dst->key, o.key, 8}, {dst->rowtime, o.ts, 8}, {dst->ordinal, o.ord, 8},
+                            {dst->values, o.val, (size_t)8 * op->c.ns}, {dst->null_mask, o.nul, 4}},
+                       epoch, cap, n);
 }
 
 int fw_over_rows_device(fw_over* op, fw_over_rows* rows, int64_t* n) {
-  if (!op || !rows || !n) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  rows->key = op->okey;
-  rows->rowtime = op->ots;
-  rows->ordinal = op->oord;
-  rows->values = op->oval;
-  rows->null_mask = op->onul;
+  const int rc = enter(op, !rows || !n);
+  if (rc) return rc;
+  rows->key = op->out.key;
+  rows->rowtime = op->out.ts;
+  rows->ordinal = op->out.ord;
+  rows->values = op->out.val;
+  rows->null_mask = op->out.nul;
   *n = op->n_out;
   return FW_OK;
 }
 
 int fw_over_clear_pending(fw_over* op) {
   if (!op) return FW_ERR_ARG;
-  op->n_out = 0;
-  op->oseg.clear();
+  clear_pending(op);
   return FW_OK;
 }
 
@@ -1504,52 +1145,40 @@ int fw_over_get_stats(fw_over* op, fw_over_stats* out) {
 
 int fw_over_snapshot_key_group(fw_over* op, int32_t kg, const fw_over_state* dst, int64_t cap_keys, int64_t cap_rows,
                                int64_t* n_keys, int64_t* n_rows) {
-  if (!op || !n_keys || !n_rows) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  if (kg < op->c.kg0 || kg >= op->c.kg0 + op->c.nkg)
-    return set_err(op, FW_ERR_KEY_GROUP, "key group %d outside KeyGroupRange [%d, %d]", kg, op->c.kg0, op->c.kg0 + op->c.nkg - 1);
-  OHIP(op, hipSetDevice(op->cfg.device));
+  int rc;
+  if ((rc = enter_key_group(op, !n_keys || !n_rows, "null argument", kg)) || (rc = on_device(op))) return rc;
   // the key group's slots and rows are picked and compacted on the device: only they cross to the host
   const int64_t ns = op->nslots, n = op->n_store;
   const int w = ov_accw(op->c), nc = op->c.nc;
   *n_keys = *n_rows = 0;
   if (ns == 0) return FW_OK;
   const ORowsD& st = op->store[op->cur];
-  int rc;
-  Buf fs, ps, fr, pr;
-  auto done = [&](int code) {
-    for (Buf* b : {&fs, &ps, &fr, &pr}) (void)hipFree(b->p);
-    return code;
-  };
+  Buf fs, ps, fr, pr;  // (freed on every way out)
   if ((rc = ensure(op, fs, (size_t)ns * 4)) || (rc = ensure(op, ps, (size_t)ns * 4)) ||
       (rc = ensure(op, fr, (size_t)std::max<int64_t>(n, 1) * 4)) || (rc = ensure(op, pr, (size_t)std::max<int64_t>(n, 1) * 4)))
-    return done(rc);
+    return rc;
   hipLaunchKernelGGL(k_ov_snap_flags, dim3(grid_of(std::max(ns, n))), dim3(256), 0, op->stream, op->map, st, ns, n, kg,
                      (uint32_t*)fs.p, (uint32_t*)fr.p);
-  if ((rc = excl_scan(op, (const uint32_t*)fs.p, (uint32_t*)ps.p, ns))) return done(rc);
+  if ((rc = excl_scan(op, (const uint32_t*)fs.p, (uint32_t*)ps.p, ns))) return rc;
   hipLaunchKernelGGL(k_ov_total, dim3(1), dim3(1), 0, op->stream, (const uint32_t*)fs.p, (const uint32_t*)ps.p, ns, op->tot);
-  if (n && (rc = excl_scan(op, (const uint32_t*)fr.p, (uint32_t*)pr.p, n))) return done(rc);
+  if (n && (rc = excl_scan(op, (const uint32_t*)fr.p, (uint32_t*)pr.p, n))) return rc;
   hipLaunchKernelGGL(k_ov_total, dim3(1), dim3(1), 0, op->stream, (const uint32_t*)fr.p, (const uint32_t*)pr.p, n, op->tot + 1);
   unsigned long long htot[2] = {0, 0};
   if (hipMemcpyAsync(htot, op->tot, 16, hipMemcpyDeviceToHost, op->stream) != hipSuccess ||
       hipStreamSynchronize(op->stream) != hipSuccess)
-    return done(set_err(op, FW_ERR_HIP, "snapshot: reading the counts failed"));
+    return set_err(op, FW_ERR_HIP, "snapshot: reading the counts failed");
   const int64_t nk = (int64_t)htot[0], nr = (int64_t)htot[1];
   *n_keys = nk;
   *n_rows = nr;
-  if (!dst || cap_keys < nk || cap_rows < nr || nk == 0) return done(FW_OK);
+  if (!dst || cap_keys < nk || cap_rows < nr || nk == 0) return FW_OK;
   // compacted: per slot {slot, key, last, acc words}, per row {slot, ts, ordinal, columns row-major, nulls}
   Buf d_ss, d_sw, d_rs, d_rw, d_rn;
-  auto done2 = [&](int code) {
-    for (Buf* b : {&d_ss, &d_sw, &d_rs, &d_rw, &d_rn}) (void)hipFree(b->p);
-    return done(code);
-  };
   const int sw = 2 + w, rw = 2 + nc;
   if ((rc = ensure(op, d_ss, (size_t)nk * 4)) || (rc = ensure(op, d_sw, (size_t)nk * 8 * sw)) ||
       (rc = ensure(op, d_rs, (size_t)std::max<int64_t>(nr, 1) * 4)) ||
       (rc = ensure(op, d_rw, (size_t)std::max<int64_t>(nr, 1) * 8 * rw)) ||
       (rc = ensure(op, d_rn, (size_t)std::max<int64_t>(nr, 1))))
-    return done2(rc);
+    return rc;
   hipLaunchKernelGGL(k_ov_snap_pack, dim3(grid_of(std::max(ns, n))), dim3(256), 0, op->stream, op->c, op->map, st, ns, n,
                      (const uint32_t*)fs.p, (const uint32_t*)ps.p, (const uint32_t*)fr.p, (const uint32_t*)pr.p,
                      (uint32_t*)d_ss.p, (int64_t*)d_sw.p, (uint32_t*)d_rs.p, (int64_t*)d_rw.p, (uint8_t*)d_rn.p);
@@ -1563,7 +1192,7 @@ int fw_over_snapshot_key_group(fw_over* op, int32_t kg, const fw_over_state* dst
     ok = hipMemcpy(hrs.data(), d_rs.p, nr * 4, hipMemcpyDeviceToHost) == hipSuccess &&
          hipMemcpy(hrw.data(), d_rw.p, (size_t)nr * 8 * rw, hipMemcpyDeviceToHost) == hipSuccess &&
          hipMemcpy(hrn.data(), d_rn.p, nr, hipMemcpyDeviceToHost) == hipSuccess;
-  if (!ok) return done2(set_err(op, FW_ERR_HIP, "snapshot: copying the key group's state failed"));
+  if (!ok) return set_err(op, FW_ERR_HIP, "snapshot: copying the key group's state failed");
   // keys in slot order; a key's rows follow each other in store (arrival) order
   std::unordered_map<uint32_t, int64_t> idx_of;
   idx_of.reserve((size_t)nk * 2);
@@ -1585,41 +1214,29 @@ int fw_over_snapshot_key_group(fw_over* op, int32_t kg, const fw_over_state* dst
     dst->nulls[d] = hrn[r];
     for (int j = 0; j < nc; j++) dst->cols[d * nc + j] = hrw[(size_t)r * rw + 2 + j];
   }
-  return done2(FW_OK);
+  return FW_OK;
 }
 
 int fw_over_restore_key_group(fw_over* op, int32_t kg, const fw_over_state* src, int64_t n_keys, int64_t n_rows) {
-  if (!op || n_keys < 0 || n_rows < 0) return op ? set_err(op, FW_ERR_ARG, "bad argument") : FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  if (kg < op->c.kg0 || kg >= op->c.kg0 + op->c.nkg)
-    return set_err(op, FW_ERR_KEY_GROUP, "key group %d outside KeyGroupRange [%d, %d]", kg, op->c.kg0, op->c.kg0 + op->c.nkg - 1);
+  int rc;
+  if ((rc = enter_key_group(op, n_keys < 0 || n_rows < 0, "bad argument", kg))) return rc;
   if (n_keys == 0) return n_rows == 0 ? FW_OK : set_err(op, FW_ERR_ARG, "rows without keys");
   if (!src || !src->key || !src->last_ts || !src->acc || !src->n_rows ||
       (n_rows > 0 && (!src->ts || !src->ordinal || !src->cols || !src->nulls)))
     return set_err(op, FW_ERR_ARG, "null column");
-  OHIP(op, hipSetDevice(op->cfg.device));
+  if ((rc = on_device(op))) return rc;
   const OCfg& c = op->c;
   const int w = ov_accw(c), nc = c.nc;
-  int64_t total = 0;
-  for (int64_t i = 0; i < n_keys; i++) {
-    if (src->n_rows[i] < 0) return set_err(op, FW_ERR_ARG, "negative n_rows");
-    total += src->n_rows[i];
-    if (c.key_kind != FW_KEY_HASHED &&
-        host_key_group(host_key_hash(src->key[i], c.key_kind == FW_KEY_INT), c.max_par) != kg)
-      return set_err(op, FW_ERR_KEY_GROUP, "key %lld is not in key group %d", (long long)src->key[i], kg);
-  }
-  if (total != n_rows) return set_err(op, FW_ERR_ARG, "n_rows does not match the keys' row counts");
+  std::unordered_set<int64_t> seen;
+  if ((rc = check_restored_keys(op, c, kg, src->key, src->n_rows, n_keys, n_rows, [](int64_t) { return FW_OK; })) ||
+      (rc = check_restored_unique(op, src->key, n_keys, seen)))
+    return rc;
   {
-    std::unordered_set<int64_t> seen;
-    for (int64_t i = 0; i < n_keys; i++)
-      if (!seen.insert(src->key[i]).second)
-        return set_err(op, FW_ERR_STATE, "key %lld occurs twice in the restored state", (long long)src->key[i]);
     std::vector<int64_t> skey(op->nslots);
-    if (op->nslots) OHIP(op, hipMemcpy(skey.data(), op->map.skey, op->nslots * 8, hipMemcpyDeviceToHost));
+    if (op->nslots) TB_HIP(op, hipMemcpy(skey.data(), op->map.skey, op->nslots * 8, hipMemcpyDeviceToHost));
     for (int64_t k : skey)
       if (seen.count(k)) return set_err(op, FW_ERR_STATE, "key %lld already has state in the handle", (long long)k);
   }
-  int rc;
   if ((rc = grow_store(op, op->n_store + n_rows))) return rc;
   if ((rc = grow_map(op, op->nslots + n_keys))) return rc;
   // rows in ordinal order (the store keeps a key's rows in arrival order), each with its key
@@ -1675,7 +1292,6 @@ int fw_over_restore_key_group(fw_over* op, int32_t kg, const fw_over_state* src,
                          (const int64_t*)rcv.p, (const uint8_t*)rn.p, n_rows);
     rc = read_ctr(op);
   }
-  for (Buf* b : {&bk, &bl, &ba, &rk, &rt, &ro, &rcv, &rn}) (void)hipFree(b->p);
   if (rc) return rc;
   op->nslots = op->hctr->nslots;
   op->n_store += n_rows;

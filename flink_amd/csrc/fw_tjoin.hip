@@ -18,27 +18,11 @@
 //              first remaining row (new timer, or the whole run is cleared when that row's time is 0) -> expired rows
 //              leave, the unjoined ones padded with the timer's time -> compaction -> the earliest timer again.
 // No thread walks a key's cache or a key's pairs: one key may hold every row.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <numeric>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <string>
-#include <unordered_set>
-#include <vector>
 
-#include "../../include/flink_window.h"
-#include "fw_keygroup.h"
+#include "fw_table.h"
 
 namespace {
-
-constexpr int64_t LMAX = INT64_MAX;
-constexpr int64_t LMIN = INT64_MIN;
-#include "fw_jmath.h"
 
 constexpr int TJ_THREADS = 256, TJ_ITEMS = 4;
 constexpr int TJ_CHUNK = TJ_THREADS * TJ_ITEMS;  // candidates a workgroup of the pair pass takes per step
@@ -78,19 +62,11 @@ struct TCtr {
   int32_t nslots, pad;
 };
 
-struct TMap {
-  int64_t* mkey;
-  uint32_t* mstate;  // 0 empty, 1 being published, 2 taken
-  uint32_t* mslot;
-  uint32_t mask;
-  // per key slot
-  int64_t* skey;
-  int32_t* skg;
+struct TMap : KeyMap {
   // per group (slot * 2 + side): the timer that cleans the side's cache (side 0, the left cache: rightTimerState),
   // and a push's first scanning / first cached row of the group (NONE outside a push)
   int64_t* tmr;
   uint32_t *fs, *fc;
-  int32_t max_keys;
 };
 
 struct TRows {  // the row store, or a run of rows to merge into it
@@ -104,79 +80,6 @@ struct TOut {
   int64_t *key, *lord, *rord, *lts, *rts, *lval, *rval, *cause, *tts;
 };
 
-// ---------------------------------------------------------------- key map (the pattern of fw_over.hip's)
-__device__ __forceinline__ uint32_t tj_home(const TMap& m, int64_t key) {
-  return (uint32_t)fmix64((uint64_t)key ^ 0x9E3779B97F4A7C15ull) & m.mask;
-}
-__device__ __forceinline__ int32_t tj_find(const TMap& m, int64_t key) {
-  uint32_t s = tj_home(m, key);
-  for (uint32_t probes = 0; probes <= m.mask; probes++) {
-    if (m.mstate[s] == 0) return -1;
-    if (m.mkey[s] == key) return (int32_t)m.mslot[s];
-    s = (s + 1) & m.mask;
-  }
-  return -1;
-}
-template <class KG>
-__device__ __forceinline__ int32_t tj_claim(const TMap& m, TCtr* ctr, int64_t key, KG kg_of) {
-  uint32_t s = tj_home(m, key);
-  for (uint32_t probes = 0; probes <= m.mask;) {
-    const uint32_t cur = __hip_atomic_load(&m.mstate[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __atomic_signal_fence(__ATOMIC_ACQUIRE);
-    if (cur == 2) {
-      if (__hip_atomic_load(&m.mkey[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == key) {
-        const uint32_t slot = __hip_atomic_load(&m.mslot[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (slot >= (uint32_t)m.max_keys) break;
-        return (int32_t)slot;
-      }
-      s = (s + 1) & m.mask;
-      probes++;
-      continue;
-    }
-    if (cur == 1) continue;  // being published by another lane: re-read
-    if (atomicCAS(&m.mstate[s], 0u, 1u) == 0u) {
-      const int32_t slot = atomicAdd(&ctr->nslots, 1);
-      __hip_atomic_store(&m.mkey[s], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&m.mslot[s], (uint32_t)slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (slot < m.max_keys) {
-        m.skey[slot] = key;
-        m.skg[slot] = kg_of();
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&m.mstate[s], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (slot >= m.max_keys) {
-        atomicAdd(&ctr->map_full, 1ull);
-        return -1;
-      }
-      return slot;
-    }
-  }
-  atomicAdd(&ctr->map_full, 1ull);
-  return -1;
-}
-__global__ __launch_bounds__(256) void k_tj_rehash(TMap m, int32_t nslots) {
-  const int32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-  if (slot >= nslots) return;
-  const int64_t key = m.skey[slot];
-  uint32_t s = tj_home(m, key);
-  for (uint32_t probes = 0; probes <= m.mask; probes++) {
-    if (atomicCAS(&m.mstate[s], 0u, 2u) == 0u) {
-      m.mkey[s] = key;
-      m.mslot[s] = (uint32_t)slot;
-      return;
-    }
-    s = (s + 1) & m.mask;
-  }
-}
-
-__device__ __forceinline__ unsigned long long wave_count(bool p) { return (unsigned long long)__popcll(__ballot(p)); }
-__device__ __forceinline__ int64_t wave_min64(int64_t v) {
-  for (int d = 32; d >= 1; d >>= 1) {
-    const int64_t o = __shfl_xor(v, d, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
 // A counting kernel runs a bounded grid whose threads stride over the rows and keep their counts in registers: one
 // atomic per wave and counter at the end, not one per 64 rows (every wave's add lands on the same address)
 constexpr int TJ_COUNT_GRID = 2048;
@@ -252,7 +155,7 @@ __global__ __launch_bounds__(256) void k_tj_classify(TCfg c, TEpoch ep, TMap m, 
     const int s = side[i] & 1, o = 1 - s;
     const int64_t t = ts[i], k = key[i];
     const int64_t ub = jadd(t, c.rel[s]);
-    const int32_t slot = tj_claim(m, ctr, k, [&] { return key_group(key_hash_of(c.key_kind, k, kh, i), c.max_par); });
+    const int32_t slot = keymap_claim(m, &ctr->nslots, &ctr->map_full, k, [&] { return key_group(key_hash_of(c.key_kind, k, kh, i), c.max_par); });
     uint32_t g = 0;
     if (slot >= 0) {
       g = (uint32_t)slot * 2u + (uint32_t)s;
@@ -713,7 +616,7 @@ __global__ __launch_bounds__(256) void k_tj_restore_keys(TCfg c, TMap m, TCtr* c
                                                          int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int32_t slot = tj_claim(m, ctr, key[i], [&] { return kg; });
+  const int32_t slot = keymap_claim(m, &ctr->nslots, &ctr->map_full, key[i], [&] { return kg; });
   if (slot < 0) return;
   m.skg[slot] = kg;
   // leftTimerState cleans the right cache (side 1), rightTimerState the left
@@ -730,7 +633,7 @@ __global__ __launch_bounds__(256) void k_tj_restore_groups(TMap m, const int64_t
                                                            int64_t n, uint32_t* __restrict__ k2, uint32_t* __restrict__ v) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int32_t slot = tj_find(m, key[i]);
+  const int32_t slot = keymap_find(m, key[i]);
   k2[i] = slot < 0 ? 0u : (uint32_t)slot * 2u + (side[i] & 1u);
   v[i] = (uint32_t)i;
 }
@@ -754,19 +657,11 @@ __global__ __launch_bounds__(256) void k_tj_iota(uint32_t* keep, uint32_t* kpos,
   kpos[i] = (uint32_t)i;
 }
 
-struct Buf {  // scratch that only grows; contents are not kept
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
 }  // namespace
 
-struct fw_tjoin {
+struct fw_tjoin : TableHandle {  // (oseg's epochs: the watermark calls so far)
   fw_tjoin_config cfg{};
   TCfg c{};
-  std::string err;
-  bool ready = false;
-  hipStream_t stream = nullptr;
   TMap map{};
   TCtr* ctr = nullptr;   // device
   TCtr* hctr = nullptr;  // pinned host copy
@@ -779,205 +674,32 @@ struct fw_tjoin {
   int64_t rows_in = 0, cached = 0, not_cached = 0, pairs = 0, pad_arr = 0, pad_scan = 0, pad_timer = 0, exp_pairs = 0,
           gate_skips = 0;
   TOut out{};
-  int64_t ocap = 0, n_out = 0, max_rows = 0;
-  std::vector<std::pair<int64_t, int64_t>> oseg;  // (epoch, rows)
-  Buf b_stage[5], b_tmp, b_pg, b_pflag, b_k1[2], b_v1[2], b_k2[2], b_v2, b_sts, b_sval, b_sflag, b_sa, b_sn, b_ba,
+  int64_t max_rows = 0;
+  Buf b_stage[5], b_pg, b_pflag, b_k1[2], b_v1[2], b_k2[2], b_v2, b_sts, b_sval, b_sflag, b_sa, b_sn, b_ba,
       b_cnt, b_off, b_bemit, b_smark, b_wgcnt, b_wgoff, b_parr, b_ppos, b_keep, b_kpos, b_pscan, b_spos, b_cf, b_cpos,
       b_due, b_tnew, b_clr;
 };
 
 namespace {
 
-int set_err(fw_tjoin* op, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  op->err = buf;
-  return code;
+// the column sets: the row store (and a run to merge), a key slot's state, the output
+Cols row_cols(TRows& r) { return Cols{col(r.g), col(r.ts), col(r.ord), col(r.val), col(r.emit)}; }
+Cols slot_cols(TMap& m) {  // (besides the key map's own skey, skg) two groups per slot; fs, fc: NONE outside a push
+  return Cols{col(m.tmr, 16, 1, 0), col(m.fs, 8, 1, 0xFF), col(m.fc, 8, 1, 0xFF)};
 }
-#define THIP(op, expr)                                                                                     \
-  do {                                                                                                     \
-    hipError_t _e = (expr);                                                                                \
-    if (_e != hipSuccess) return set_err(op, FW_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
-
-inline unsigned grid_of(int64_t n, int t = 256) { return (unsigned)std::max<int64_t>(1, (n + t - 1) / t); }
-
-int ensure(fw_tjoin* op, Buf& b, size_t bytes) {
-  if (bytes <= b.cap) return FW_OK;
-  size_t want = std::max(bytes, b.cap + b.cap / 2);
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  if (hipMalloc(&b.p, want) != hipSuccess) {
-    (void)hipGetLastError();
-    b.p = nullptr;
-    return set_err(op, FW_ERR_CAPACITY, "cannot allocate %zu bytes of scratch", want);
-  }
-  b.cap = want;
-  return FW_OK;
+Cols out_cols(TOut& o) {
+  return Cols{col(o.key), col(o.lord), col(o.rord), col(o.lts), col(o.rts), col(o.lval), col(o.rval), col(o.cause), col(o.tts)};
 }
 
-void free_rows(TRows& r) {
-  (void)hipFree(r.g);
-  (void)hipFree(r.ts);
-  (void)hipFree(r.ord);
-  (void)hipFree(r.val);
-  (void)hipFree(r.emit);
-  r = TRows{};
-}
-int alloc_rows(fw_tjoin* op, TRows& r, int64_t cap) {
-  r = TRows{};
-  r.cap = cap;
-  const size_t n = (size_t)cap;
-  if (hipMalloc(&r.g, n * 4) != hipSuccess || hipMalloc(&r.ts, n * 8) != hipSuccess ||
-      hipMalloc(&r.ord, n * 8) != hipSuccess || hipMalloc(&r.val, n * 8) != hipSuccess ||
-      hipMalloc(&r.emit, n) != hipSuccess) {
-    (void)hipGetLastError();
-    free_rows(r);
-    return set_err(op, FW_ERR_CAPACITY, "cannot allocate a row store of %lld rows", (long long)cap);
-  }
-  return FW_OK;
-}
-// both store buffers to at least `need` rows; the live one keeps its rows
-int grow_store(fw_tjoin* op, int64_t need) {
-  if (need <= op->store[0].cap) return FW_OK;
-  if (need >= (int64_t(1) << 31)) return set_err(op, FW_ERR_CAPACITY, "the row store would exceed 2^31 rows");
-  int64_t cap = std::max<int64_t>(op->store[0].cap, 1024);
-  while (cap < need) cap *= 2;
-  TRows a, b;
-  int rc = alloc_rows(op, a, cap);
-  if (rc) return rc;
-  rc = alloc_rows(op, b, cap);
-  if (rc) {
-    free_rows(a);
-    return rc;
-  }
-  const TRows& o = op->store[op->cur];
-  const size_t n = (size_t)op->n_store;
-  if (n) {
-    THIP(op, hipMemcpyAsync(a.g, o.g, n * 4, hipMemcpyDeviceToDevice, op->stream));
-    THIP(op, hipMemcpyAsync(a.ts, o.ts, n * 8, hipMemcpyDeviceToDevice, op->stream));
-    THIP(op, hipMemcpyAsync(a.ord, o.ord, n * 8, hipMemcpyDeviceToDevice, op->stream));
-    THIP(op, hipMemcpyAsync(a.val, o.val, n * 8, hipMemcpyDeviceToDevice, op->stream));
-    THIP(op, hipMemcpyAsync(a.emit, o.emit, n, hipMemcpyDeviceToDevice, op->stream));
-    THIP(op, hipStreamSynchronize(op->stream));
-  }
-  free_rows(op->store[0]);
-  free_rows(op->store[1]);
-  op->store[0] = a;
-  op->store[1] = b;
-  op->cur = 0;
-  return FW_OK;
-}
-int grow_run(fw_tjoin* op, int64_t need) {
+int grow_store(fw_tjoin* op, int64_t need) { return grow_store(op, op->store, op->cur, op->n_store, need, row_cols); }
+int grow_run(fw_tjoin* op, int64_t need) {  // (contents are not kept)
   if (need <= op->run.cap) return FW_OK;
-  int64_t cap = std::max<int64_t>(op->run.cap, 1024);
-  while (cap < need) cap *= 2;
-  THIP(op, hipStreamSynchronize(op->stream));
-  free_rows(op->run);
-  return alloc_rows(op, op->run, cap);
+  const int rc = settle(op);
+  return rc ? rc : cols_grow(op, op->run, op->run.cap, need, 0, row_cols, "cannot allocate a row store of %lld rows");
 }
-
-void free_map(TMap& m) {
-  (void)hipFree(m.mkey);
-  (void)hipFree(m.mstate);
-  (void)hipFree(m.mslot);
-  (void)hipFree(m.skey);
-  (void)hipFree(m.skg);
-  (void)hipFree(m.tmr);
-  (void)hipFree(m.fs);
-  (void)hipFree(m.fc);
-  m = TMap{};
-}
-// a key map for at least `keys` keys (load <= 1/2); the slots' state moves over and the map is rebuilt from their keys
-int grow_map(fw_tjoin* op, int64_t keys) {
-  if (keys <= op->map.max_keys) return FW_OK;
-  if (keys >= (int64_t(1) << 29)) return set_err(op, FW_ERR_CAPACITY, "the key map would exceed 2^29 keys");
-  int64_t mk = std::max<int64_t>(op->map.max_keys, 1024);
-  while (mk < keys) mk *= 2;
-  const int64_t cap = mk * 2;
-  TMap n{};
-  n.mask = (uint32_t)(cap - 1);
-  n.max_keys = (int32_t)mk;
-  if (hipMalloc(&n.mkey, cap * 8) != hipSuccess || hipMalloc(&n.mstate, cap * 4) != hipSuccess ||
-      hipMalloc(&n.mslot, cap * 4) != hipSuccess || hipMalloc(&n.skey, mk * 8) != hipSuccess ||
-      hipMalloc(&n.skg, mk * 4) != hipSuccess || hipMalloc(&n.tmr, mk * 16) != hipSuccess ||
-      hipMalloc(&n.fs, mk * 8) != hipSuccess || hipMalloc(&n.fc, mk * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    free_map(n);
-    return set_err(op, FW_ERR_CAPACITY, "cannot allocate a key map of %lld keys", (long long)mk);
-  }
-  THIP(op, hipMemsetAsync(n.mstate, 0, cap * 4, op->stream));
-  THIP(op, hipMemsetAsync(n.tmr, 0, mk * 16, op->stream));
-  THIP(op, hipMemsetAsync(n.fs, 0xFF, mk * 8, op->stream));
-  THIP(op, hipMemsetAsync(n.fc, 0xFF, mk * 8, op->stream));
-  const int64_t ns = op->nslots;
-  if (ns) {
-    const TMap& o = op->map;
-    THIP(op, hipMemcpyAsync(n.skey, o.skey, ns * 8, hipMemcpyDeviceToDevice, op->stream));
-    THIP(op, hipMemcpyAsync(n.skg, o.skg, ns * 4, hipMemcpyDeviceToDevice, op->stream));
-    THIP(op, hipMemcpyAsync(n.tmr, o.tmr, ns * 16, hipMemcpyDeviceToDevice, op->stream));
-    hipLaunchKernelGGL(k_tj_rehash, dim3(grid_of(ns)), dim3(256), 0, op->stream, n, (int32_t)ns);
-  }
-  THIP(op, hipStreamSynchronize(op->stream));
-  free_map(op->map);
-  op->map = n;
-  return FW_OK;
-}
-
+int grow_map(fw_tjoin* op, int64_t keys) { return grow_map(op, op->map, op->nslots, keys, 29, slot_cols); }
 int grow_out(fw_tjoin* op, int64_t need) {
-  if (need <= op->ocap) return FW_OK;
-  int64_t cap = std::max<int64_t>(op->ocap, 1024);
-  while (cap < need) cap *= 2;
-  int64_t* col[9] = {};
-  int64_t** cur[9] = {&op->out.key, &op->out.lord, &op->out.rord, &op->out.lts, &op->out.rts,
-                      &op->out.lval, &op->out.rval, &op->out.cause, &op->out.tts};
-  for (int q = 0; q < 9; q++)
-    if (hipMalloc(&col[q], (size_t)cap * 8) != hipSuccess) {
-      (void)hipGetLastError();
-      for (int z = 0; z < q; z++) (void)hipFree(col[z]);
-      return set_err(op, FW_ERR_CAPACITY, "cannot allocate an output buffer of %lld rows", (long long)cap);
-    }
-  const size_t n = (size_t)op->n_out;
-  if (n) {
-    for (int q = 0; q < 9; q++) THIP(op, hipMemcpyAsync(col[q], *cur[q], n * 8, hipMemcpyDeviceToDevice, op->stream));
-  }
-  THIP(op, hipStreamSynchronize(op->stream));
-  for (int q = 0; q < 9; q++) {
-    (void)hipFree(*cur[q]);
-    *cur[q] = col[q];
-  }
-  op->ocap = cap;
-  return FW_OK;
-}
-
-// the device counters to the host (settles the stream)
-int read_ctr(fw_tjoin* op) {
-  THIP(op, hipMemcpyAsync(op->hctr, op->ctr, sizeof(TCtr), hipMemcpyDeviceToHost, op->stream));
-  THIP(op, hipStreamSynchronize(op->stream));
-  return FW_OK;
-}
-
-template <class T>
-int excl_scan(fw_tjoin* op, const T* in, T* out, int64_t n) {
-  size_t bytes = 0;
-  THIP(op, rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), (size_t)n, rocprim::plus<T>(), op->stream));
-  int rc = ensure(op, op->b_tmp, bytes);
-  if (rc) return rc;
-  THIP(op, rocprim::exclusive_scan(op->b_tmp.p, bytes, in, out, T(0), (size_t)n, rocprim::plus<T>(), op->stream));
-  return FW_OK;
-}
-template <class K>
-int sort_pairs(fw_tjoin* op, const K* kin, K* kout, const uint32_t* vin, uint32_t* vout, int64_t n, unsigned end_bit) {
-  size_t bytes = 0;
-  THIP(op, rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, (size_t)n, 0u, end_bit, op->stream));
-  int rc = ensure(op, op->b_tmp, bytes);
-  if (rc) return rc;
-  THIP(op, rocprim::radix_sort_pairs(op->b_tmp.p, bytes, kin, kout, vin, vout, (size_t)n, 0u, end_bit, op->stream));
-  return FW_OK;
+  return cols_grow(op, op->out, op->ocap, need, op->n_out, out_cols, "cannot allocate an output buffer of %lld rows");
 }
 unsigned group_bits(const fw_tjoin* op) {
   unsigned b = 1;
@@ -1142,10 +864,7 @@ int do_push(fw_tjoin* op, const uint8_t* side, const int64_t* key, const int64_t
     for (int s = 0; s < 2; s++)
       if (h.first[s] != LMAX) op->X[1 - s] = ep.E[1 - s];  // a row of side s passed the gate: the other cache's time
     op->n_out += nrows;
-    if (nrows) {
-      if (!op->oseg.empty() && op->oseg.back().first == op->wm_calls) op->oseg.back().second += nrows;
-      else op->oseg.emplace_back(op->wm_calls, nrows);
-    }
+    append_segment(op, op->wm_calls, nrows);
     op->rows_in += n;
     op->ord_base += n;
     op->cached += ncached;
@@ -1189,7 +908,7 @@ int do_watermark(fw_tjoin* op, int64_t wm, int64_t* n_rows) {
     return rc;
   const TRows& st = op->store[op->cur];
   const unsigned gs = grid_of(ns), gg = grid_of(ng);
-  THIP(op, hipMemsetAsync(&op->ctr->fired[0], 0, 16, sm));
+  TB_HIP(op, hipMemsetAsync(&op->ctr->fired[0], 0, 16, sm));
   hipLaunchKernelGGL(k_tj_due, dim3(gg), dim3(256), 0, sm, op->map, ng, wm, TJ_U8(op->b_due), TJ_I64(op->b_tnew),
                      TJ_U8(op->b_clr), op->ctr);
   if (ns) {
@@ -1225,7 +944,7 @@ int do_watermark(fw_tjoin* op, int64_t wm, int64_t* n_rows) {
     if (fired[s]) op->X[s] = ep.E[s];
   op->n_out += npad;
   op->pad_timer += npad;
-  if (npad) op->oseg.emplace_back(call, npad);
+  append_segment(op, call, npad);
   if (n_rows) *n_rows = npad;
   return FW_OK;
 }
@@ -1239,6 +958,7 @@ int fw_tjoin_create(const fw_tjoin_config* cfg, fw_tjoin** out) {
   *out = nullptr;
   fw_tjoin* op = new fw_tjoin();
   op->cfg = *cfg;
+  op->device = cfg->device;
   const fw_tjoin_config& c = *cfg;
   auto fail = [&](int code, const char* msg) {  // as fw_create: the handle carries the message; destroy it
     op->err = msg;
@@ -1279,17 +999,16 @@ int fw_tjoin_create(const fw_tjoin_config* cfg, fw_tjoin** out) {
     (void)hipGetLastError();
     return set_err(op, FW_ERR_HIP, "device %d is not available (%d devices)", c.device, ndev);
   }
-  THIP(op, hipSetDevice(c.device));
-  THIP(op, hipStreamCreateWithFlags(&op->stream, hipStreamNonBlocking));
-  THIP(op, hipMalloc(&op->ctr, sizeof(TCtr)));
-  THIP(op, hipHostMalloc(&op->hctr, sizeof(TCtr)));
+  TB_HIP(op, hipSetDevice(c.device));
+  TB_HIP(op, hipStreamCreateWithFlags(&op->stream, hipStreamNonBlocking));
+  TB_HIP(op, hipMalloc(&op->ctr, sizeof(TCtr)));
+  TB_HIP(op, hipHostMalloc(&op->hctr, sizeof(TCtr)));
   memset(op->hctr, 0, sizeof(TCtr));
   op->hctr->next_due = LMAX;
   op->hctr->first[0] = op->hctr->first[1] = LMAX;
-  THIP(op, hipMemcpyAsync(op->ctr, op->hctr, sizeof(TCtr), hipMemcpyHostToDevice, op->stream));
-  THIP(op, hipStreamSynchronize(op->stream));
-  const int64_t mb = c.max_batch > 0 ? c.max_batch : (int64_t(1) << 16);
   int rc;
+  if ((rc = write_ctr(op))) return rc;
+  const int64_t mb = c.max_batch > 0 ? c.max_batch : (int64_t(1) << 16);
   if ((rc = grow_map(op, std::max<int64_t>(c.expected_keys, 1024)))) return rc;
   if ((rc = grow_store(op, mb))) return rc;
   if ((rc = grow_run(op, mb))) return rc;
@@ -1300,24 +1019,13 @@ int fw_tjoin_create(const fw_tjoin_config* cfg, fw_tjoin** out) {
 void fw_tjoin_destroy(fw_tjoin* op) {
   if (!op) return;
   if (op->stream) {
-    (void)hipSetDevice(op->cfg.device);
+    (void)hipSetDevice(op->device);
     (void)hipStreamSynchronize(op->stream);
-    free_map(op->map);
-    free_rows(op->store[0]);
-    free_rows(op->store[1]);
-    free_rows(op->run);
+    free_map(op->map, slot_cols);
+    for (TRows* r : {&op->store[0], &op->store[1], &op->run}) cols_free(row_cols(*r));
+    cols_free(out_cols(op->out));
     (void)hipFree(op->ctr);
     (void)hipHostFree(op->hctr);
-    for (int64_t* p : {op->out.key, op->out.lord, op->out.rord, op->out.lts, op->out.rts, op->out.lval, op->out.rval,
-                       op->out.cause, op->out.tts})
-      (void)hipFree(p);
-    Buf* all[] = {&op->b_stage[0], &op->b_stage[1], &op->b_stage[2], &op->b_stage[3], &op->b_stage[4], &op->b_tmp,
-                  &op->b_pg, &op->b_pflag, &op->b_k1[0], &op->b_k1[1], &op->b_v1[0], &op->b_v1[1], &op->b_k2[0],
-                  &op->b_k2[1], &op->b_v2, &op->b_sts, &op->b_sval, &op->b_sflag, &op->b_sa, &op->b_sn, &op->b_ba,
-                  &op->b_cnt, &op->b_off, &op->b_bemit, &op->b_smark, &op->b_wgcnt, &op->b_wgoff, &op->b_parr,
-                  &op->b_ppos, &op->b_keep, &op->b_kpos, &op->b_pscan, &op->b_spos, &op->b_cf, &op->b_cpos, &op->b_due,
-                  &op->b_tnew, &op->b_clr};
-    for (Buf* b : all) (void)hipFree(b->p);
     (void)hipStreamDestroy(op->stream);
   }
   delete op;
@@ -1327,31 +1035,23 @@ const char* fw_tjoin_last_error(const fw_tjoin* op) { return op ? op->err.c_str(
 
 int fw_tjoin_push_batch_device(fw_tjoin* op, const uint8_t* side, const int64_t* key, const int64_t* rowtime,
                                const int64_t* val, const int32_t* key_hash, int64_t n) {
-  if (!op) return FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  if (n < 0 || (n > 0 && (!side || !key || !rowtime))) return set_err(op, FW_ERR_ARG, "null column");
-  if (op->c.key_kind == FW_KEY_HASHED && n > 0 && !key_hash)
-    return set_err(op, FW_ERR_ARG, "key_hash required for FW_KEY_HASHED");
-  THIP(op, hipSetDevice(op->cfg.device));
+  int rc;
+  if ((rc = enter_push(op, !side || !key || !rowtime, key_hash, n)) || (rc = on_device(op))) return rc;
   return do_push(op, side, key, rowtime, val, key_hash, n);
 }
 
 int fw_tjoin_push_batch(fw_tjoin* op, const uint8_t* side, const int64_t* key, const int64_t* rowtime,
                         const int64_t* val, const int32_t* key_hash, int64_t n) {
-  if (!op) return FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  if (n < 0 || (n > 0 && (!side || !key || !rowtime))) return set_err(op, FW_ERR_ARG, "null column");
-  if (op->c.key_kind == FW_KEY_HASHED && n > 0 && !key_hash)
-    return set_err(op, FW_ERR_ARG, "key_hash required for FW_KEY_HASHED");
+  int rc;
+  if ((rc = enter_push(op, !side || !key || !rowtime, key_hash, n))) return rc;
   if (n == 0) return FW_OK;
-  THIP(op, hipSetDevice(op->cfg.device));
+  if ((rc = on_device(op))) return rc;
   const size_t sz[5] = {(size_t)n, (size_t)n * 8, (size_t)n * 8, (size_t)n * 8, (size_t)n * 4};
   const void* src[5] = {side, key, rowtime, val, key_hash};
-  int rc;
   for (int q = 0; q < 5; q++) {
     if (!src[q]) continue;
     if ((rc = ensure(op, op->b_stage[q], sz[q]))) return rc;
-    THIP(op, hipMemcpyAsync(op->b_stage[q].p, src[q], sz[q], hipMemcpyHostToDevice, op->stream));
+    TB_HIP(op, hipMemcpyAsync(op->b_stage[q].p, src[q], sz[q], hipMemcpyHostToDevice, op->stream));
   }
   // the staging copies run ahead of do_push's kernels on the same stream; its one read settles them too
   rc = do_push(op, (const uint8_t*)op->b_stage[0].p, (const int64_t*)op->b_stage[1].p, (const int64_t*)op->b_stage[2].p,
@@ -1361,12 +1061,10 @@ int fw_tjoin_push_batch(fw_tjoin* op, const uint8_t* side, const int64_t* key, c
 }
 
 int fw_tjoin_advance_watermark(fw_tjoin* op, int64_t wm, int64_t* n_rows, int64_t* forwarded_wm) {
-  if (!op) return FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
+  int rc;
+  if ((rc = enter(op))) return rc;
   if (wm < op->wm) return set_err(op, FW_ERR_ARG, "watermark %lld is lower than the current %lld", (long long)wm, (long long)op->wm);
-  THIP(op, hipSetDevice(op->cfg.device));
-  const int rc = do_watermark(op, wm, n_rows);
-  if (rc) return rc;
+  if ((rc = on_device(op)) || (rc = do_watermark(op, wm, n_rows))) return rc;
   // getMaxOutputDelay; the subtraction wraps as the reference's does
   if (forwarded_wm)
     *forwarded_wm = (int64_t)((uint64_t)wm - (uint64_t)(std::max(op->c.rel[0], op->c.rel[1]) + op->c.L));
@@ -1374,47 +1072,18 @@ int fw_tjoin_advance_watermark(fw_tjoin* op, int64_t wm, int64_t* n_rows, int64_
 }
 
 int fw_tjoin_drain(fw_tjoin* op, const fw_tjoin_rows* dst, int64_t* epoch, int64_t cap, int64_t* n) {
-  if (!op || !dst || !n || cap < 0) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  THIP(op, hipSetDevice(op->cfg.device));
-  const int64_t k = std::min(cap, op->n_out);
-  *n = k;
-  if (k == 0) return FW_OK;
-  int64_t* to[9] = {dst->key, dst->left_ord, dst->right_ord, dst->left_rowtime, dst->right_rowtime,
-                    dst->left_val, dst->right_val, dst->cause_ord, dst->timer_ts};
-  int64_t* from[9] = {op->out.key, op->out.lord, op->out.rord, op->out.lts, op->out.rts,
-                      op->out.lval, op->out.rval, op->out.cause, op->out.tts};
-  for (int q = 0; q < 9; q++)
-    if (to[q]) THIP(op, hipMemcpyAsync(to[q], from[q], (size_t)k * 8, hipMemcpyDeviceToHost, op->stream));
-  const int64_t left = op->n_out - k;
-  THIP(op, hipStreamSynchronize(op->stream));
-  if (left) {  // (a partial drain: the rest moves to the front through a bounce buffer)
-    int rc;
-    if ((rc = ensure(op, op->b_tmp, (size_t)left * 8))) return rc;
-    for (int q = 0; q < 9; q++) {
-      THIP(op, hipMemcpyAsync(op->b_tmp.p, from[q] + k, (size_t)left * 8, hipMemcpyDeviceToDevice, op->stream));
-      THIP(op, hipMemcpyAsync(from[q], op->b_tmp.p, (size_t)left * 8, hipMemcpyDeviceToDevice, op->stream));
-    }
-    THIP(op, hipStreamSynchronize(op->stream));
-  }
-  int64_t w = 0;
-  while (w < k && !op->oseg.empty()) {
-    auto& s = op->oseg.front();
-    const int64_t take = std::min(s.second, k - w);
-    if (epoch) std::fill(epoch + w, epoch + w + take, s.first);
-    w += take;
-    s.second -= take;
-    if (s.second == 0) op->oseg.erase(op->oseg.begin());
-  }
-  op->n_out = left;
-  return FW_OK;
+  int rc;
+  if ((rc = enter(op, !dst || !n || cap < 0)) || (rc = on_device(op))) return rc;
+  const TOut& o = op->out;
+  return drain_pending(op, {{dst->key, o.key, 8}, {dst->left_ord, o.lord, 8}, {dst->right_ord, o.rord, 8},
+                            {dst->left_rowtime, o.lts, 8}, {dst->right_rowtime, o.rts, 8}, {dst->left_val, o.lval, 8},
+                            {dst->right_val, o.rval, 8}, {dst->cause_ord, o.cause, 8}, {dst->timer_ts, o.tts, 8}},
+                       epoch, cap, n);
 }
 
 int fw_tjoin_rows_device(fw_tjoin* op, fw_tjoin_rows* rows, int64_t* n) {
-  if (!op || !rows || !n) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  THIP(op, hipSetDevice(op->cfg.device));
-  THIP(op, hipStreamSynchronize(op->stream));
+  int rc;
+  if ((rc = enter(op, !rows || !n)) || (rc = on_device(op)) || (rc = settle(op))) return rc;
   rows->key = op->out.key;
   rows->left_ord = op->out.lord;
   rows->right_ord = op->out.rord;
@@ -1430,8 +1099,7 @@ int fw_tjoin_rows_device(fw_tjoin* op, fw_tjoin_rows* rows, int64_t* n) {
 
 int fw_tjoin_clear_pending(fw_tjoin* op) {
   if (!op) return FW_ERR_ARG;
-  op->n_out = 0;
-  op->oseg.clear();
+  clear_pending(op);
   return FW_OK;
 }
 
@@ -1439,9 +1107,8 @@ int fw_tjoin_get_stats(fw_tjoin* op, fw_tjoin_stats* out) {
   if (!op || !out) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
   memset(out, 0, sizeof *out);
   if (op->ready) {
-    THIP(op, hipSetDevice(op->cfg.device));
-    const int rc = read_ctr(op);
-    if (rc) return rc;
+    int rc;
+    if ((rc = on_device(op)) || (rc = read_ctr(op))) return rc;
     out->timers_set = (int64_t)op->hctr->timers_set;
     out->active_timers = op->hctr->active_timers;
   }
@@ -1462,12 +1129,9 @@ int fw_tjoin_get_stats(fw_tjoin* op, fw_tjoin_stats* out) {
 
 int fw_tjoin_snapshot_key_group(fw_tjoin* op, int32_t kg, const fw_tjoin_state* dst, int64_t cap_keys, int64_t cap_rows,
                                 int64_t* n_keys, int64_t* n_rows) {
-  if (!op || !n_keys || !n_rows) return op ? set_err(op, FW_ERR_ARG, "null argument") : FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  if (kg < op->c.kg0 || kg >= op->c.kg0 + op->c.nkg)
-    return set_err(op, FW_ERR_KEY_GROUP, "key group %d outside KeyGroupRange [%d, %d]", kg, op->c.kg0, op->c.kg0 + op->c.nkg - 1);
-  THIP(op, hipSetDevice(op->cfg.device));
-  THIP(op, hipStreamSynchronize(op->stream));
+  int rc;
+  if ((rc = enter_key_group(op, !n_keys || !n_rows, "null argument", kg)) || (rc = on_device(op)) || (rc = settle(op)))
+    return rc;
   *n_keys = *n_rows = 0;
   const int64_t nsl = op->nslots, ns = op->n_store;
   if (nsl == 0) return FW_OK;
@@ -1475,12 +1139,12 @@ int fw_tjoin_snapshot_key_group(fw_tjoin* op, int32_t kg, const fw_tjoin_state* 
   // group's keys (those with a timer set; a cache with rows always has its timer) and their rows
   std::vector<int64_t> skey(nsl), tmr(2 * nsl);
   std::vector<int32_t> skg(nsl);
-  THIP(op, hipMemcpy(skey.data(), op->map.skey, nsl * 8, hipMemcpyDeviceToHost));
-  THIP(op, hipMemcpy(skg.data(), op->map.skg, nsl * 4, hipMemcpyDeviceToHost));
-  THIP(op, hipMemcpy(tmr.data(), op->map.tmr, nsl * 16, hipMemcpyDeviceToHost));
+  TB_HIP(op, hipMemcpy(skey.data(), op->map.skey, nsl * 8, hipMemcpyDeviceToHost));
+  TB_HIP(op, hipMemcpy(skg.data(), op->map.skg, nsl * 4, hipMemcpyDeviceToHost));
+  TB_HIP(op, hipMemcpy(tmr.data(), op->map.tmr, nsl * 16, hipMemcpyDeviceToHost));
   const TRows& st = op->store[op->cur];
   std::vector<uint32_t> g(ns);
-  if (ns) THIP(op, hipMemcpy(g.data(), st.g, ns * 4, hipMemcpyDeviceToHost));
+  if (ns) TB_HIP(op, hipMemcpy(g.data(), st.g, ns * 4, hipMemcpyDeviceToHost));
   std::vector<int64_t> idx(nsl, -1), cnt;
   int64_t nk = 0, nr = 0;
   for (int64_t s = 0; s < nsl; s++)
@@ -1499,10 +1163,10 @@ int fw_tjoin_snapshot_key_group(fw_tjoin* op, int32_t kg, const fw_tjoin_state* 
   std::vector<int64_t> ts(ns), ord(ns), val(ns);
   std::vector<uint8_t> em(ns);
   if (ns) {
-    THIP(op, hipMemcpy(ts.data(), st.ts, ns * 8, hipMemcpyDeviceToHost));
-    THIP(op, hipMemcpy(ord.data(), st.ord, ns * 8, hipMemcpyDeviceToHost));
-    THIP(op, hipMemcpy(val.data(), st.val, ns * 8, hipMemcpyDeviceToHost));
-    THIP(op, hipMemcpy(em.data(), st.emit, ns, hipMemcpyDeviceToHost));
+    TB_HIP(op, hipMemcpy(ts.data(), st.ts, ns * 8, hipMemcpyDeviceToHost));
+    TB_HIP(op, hipMemcpy(ord.data(), st.ord, ns * 8, hipMemcpyDeviceToHost));
+    TB_HIP(op, hipMemcpy(val.data(), st.val, ns * 8, hipMemcpyDeviceToHost));
+    TB_HIP(op, hipMemcpy(em.data(), st.emit, ns, hipMemcpyDeviceToHost));
   }
   std::vector<int64_t> fill(nk, 0);
   for (int64_t i = 1; i < nk; i++) fill[i] = fill[i - 1] + cnt[i - 1];
@@ -1528,27 +1192,18 @@ int fw_tjoin_snapshot_key_group(fw_tjoin* op, int32_t kg, const fw_tjoin_state* 
 }
 
 int fw_tjoin_restore_key_group(fw_tjoin* op, int32_t kg, const fw_tjoin_state* src, int64_t n_keys, int64_t n_rows) {
-  if (!op || n_keys < 0 || n_rows < 0) return op ? set_err(op, FW_ERR_ARG, "bad argument") : FW_ERR_ARG;
-  if (!op->ready) return set_err(op, FW_ERR_STATE, "the handle was not created");
-  if (kg < op->c.kg0 || kg >= op->c.kg0 + op->c.nkg)
-    return set_err(op, FW_ERR_KEY_GROUP, "key group %d outside KeyGroupRange [%d, %d]", kg, op->c.kg0, op->c.kg0 + op->c.nkg - 1);
+  int rc;
+  if ((rc = enter_key_group(op, n_keys < 0 || n_rows < 0, "bad argument", kg))) return rc;
   if (n_keys == 0) return n_rows == 0 ? FW_OK : set_err(op, FW_ERR_ARG, "rows without keys");
   if (!src || !src->key || !src->left_timer || !src->right_timer || !src->n_rows ||
       (n_rows > 0 && (!src->side || !src->rowtime || !src->ordinal || !src->val || !src->emitted)))
     return set_err(op, FW_ERR_ARG, "null column");
-  THIP(op, hipSetDevice(op->cfg.device));
-  THIP(op, hipStreamSynchronize(op->stream));
+  if ((rc = on_device(op)) || (rc = settle(op))) return rc;
   const TCfg& c = op->c;
-  int64_t total = 0;
-  for (int64_t i = 0; i < n_keys; i++) {
-    if (src->n_rows[i] < 0) return set_err(op, FW_ERR_ARG, "negative n_rows");
-    if (src->left_timer[i] < 0 || src->right_timer[i] < 0) return set_err(op, FW_ERR_ARG, "negative timer");
-    total += src->n_rows[i];
-    if (c.key_kind != FW_KEY_HASHED &&
-        host_key_group(host_key_hash(src->key[i], c.key_kind == FW_KEY_INT), c.max_par) != kg)
-      return set_err(op, FW_ERR_KEY_GROUP, "key %lld is not in key group %d", (long long)src->key[i], kg);
-  }
-  if (total != n_rows) return set_err(op, FW_ERR_ARG, "n_rows does not match the keys' row counts");
+  rc = check_restored_keys(op, c, kg, src->key, src->n_rows, n_keys, n_rows, [&](int64_t i) {
+    return src->left_timer[i] < 0 || src->right_timer[i] < 0 ? set_err(op, FW_ERR_ARG, "negative timer") : FW_OK;
+  });
+  if (rc) return rc;
   int64_t max_ord = -1;
   for (int64_t r = 0; r < n_rows; r++) {
     if (src->side[r] > 1) return set_err(op, FW_ERR_ARG, "a restored row has a side outside {0, 1}");
@@ -1565,20 +1220,17 @@ int fw_tjoin_restore_key_group(fw_tjoin* op, int32_t kg, const fw_tjoin_state* s
                        src->side[r] == 0 ? "left" : "right", src->side[r] == 0 ? "right_timer" : "left_timer");
   {
     std::unordered_set<int64_t> seen;
-    for (int64_t i = 0; i < n_keys; i++)
-      if (!seen.insert(src->key[i]).second)
-        return set_err(op, FW_ERR_STATE, "key %lld occurs twice in the restored state", (long long)src->key[i]);
+    if ((rc = check_restored_unique(op, src->key, n_keys, seen))) return rc;
     const int64_t nsl = op->nslots;
     std::vector<int64_t> skey(nsl), tmr(2 * nsl);
     if (nsl) {
-      THIP(op, hipMemcpy(skey.data(), op->map.skey, nsl * 8, hipMemcpyDeviceToHost));
-      THIP(op, hipMemcpy(tmr.data(), op->map.tmr, nsl * 16, hipMemcpyDeviceToHost));
+      TB_HIP(op, hipMemcpy(skey.data(), op->map.skey, nsl * 8, hipMemcpyDeviceToHost));
+      TB_HIP(op, hipMemcpy(tmr.data(), op->map.tmr, nsl * 16, hipMemcpyDeviceToHost));
     }
     for (int64_t s = 0; s < nsl; s++)
       if ((tmr[2 * s] | tmr[2 * s + 1]) != 0 && seen.count(skey[s]))
         return set_err(op, FW_ERR_STATE, "key %lld already has state in the handle", (long long)skey[s]);
   }
-  int rc;
   if ((rc = grow_map(op, op->nslots + n_keys))) return rc;
   if ((rc = grow_store(op, op->n_store + n_rows))) return rc;
   if ((rc = grow_run(op, std::max<int64_t>(n_rows, 1)))) return rc;
@@ -1651,7 +1303,6 @@ int fw_tjoin_restore_key_group(fw_tjoin* op, int32_t kg, const fw_tjoin_state* s
     if (!rc) rc = read_ctr(op);
     if (rc) op->ready = false;
   }
-  for (Buf* b : {&bk, &bl, &br, &rk, &rt, &ro, &rv, &rs, &re}) (void)hipFree(b->p);
   if (rc) return rc;
   op->nslots = op->hctr->nslots;
   op->next_due = op->hctr->next_due;

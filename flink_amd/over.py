@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from ._handle import _TableHandle
 from .table import _decode
 from .windowing import FLOAT_TYPES, ROW_FUNCTIONS, VALUE_TYPES, _ms
 
@@ -58,30 +59,21 @@ def over_config(frame, column_types, aggregates, key_type="long", max_parallelis
     return c
 
 
-class OverAggregate:
+class OverAggregate(_TableHandle):
     """One keyed row-time OVER aggregation.  `column_types`: the aggregated columns' types ("long", "int", "short",
     "byte", "double"; "float" for COUNT / MIN / MAX only); `aggregates`: [(function, column index)], function one of
     count_star, count, sum, min, max, avg.  process(keys, rowtimes, columns, nulls[, key_hash]) takes numpy arrays or
     CUDA tensors; watermark(wm) returns the rows it emits as [(key, rowtime, ordinal, [values, None = NULL])], a key's
     rows in (rowtime, arrival) order."""
+    _prefix, _Rows, _Stats = "fw_over", N.FwOverRows, N.FwOverStats
 
     def __init__(self, frame, column_types, aggregates, key_type="long", **kw):
         self.column_types = tuple(column_types)
         self.aggregates = tuple((f, int(c)) for f, c in aggregates)
         self.frame = frame
         cfg = over_config(frame, self.column_types, self.aggregates, key_type=key_type, **kw)
-        self._h = ctypes.c_void_p()
-        rc = N.lib().fw_over_create(ctypes.byref(cfg), ctypes.byref(self._h))
-        if rc != N.FW_OK:
-            msg = N.lib().fw_over_last_error(self._h).decode() if self._h else "error"
-            N.lib().fw_over_destroy(self._h)
-            self._h = None
-            raise N.NativeError(rc, msg)
+        self._create(cfg)
         self.epoch = 0
-
-    def _check(self, rc):
-        if rc != N.FW_OK:
-            raise N.NativeError(rc, N.lib().fw_over_last_error(self._h).decode())
 
     def process(self, keys, rowtimes, columns, nulls=None, key_hash=None):
         L = N.lib()
@@ -135,12 +127,7 @@ class OverAggregate:
     def rows_device(self):
         """The pending output rows where they are, in HBM: (FwOverRows of device pointers, rows).  Valid until the
         next call on the handle; the rows stay pending (clear_pending() discards them)."""
-        rows, n = N.FwOverRows(), ctypes.c_int64()
-        self._check(N.lib().fw_over_rows_device(self._h, ctypes.byref(rows), ctypes.byref(n)))
-        return rows, n.value
-
-    def clear_pending(self):
-        self._check(N.lib().fw_over_clear_pending(self._h))
+        return self._rows_device()
 
     def drain_arrays(self):
         """The pending output rows as arrays: key, rowtime, ordinal, values [rows, aggregates], null_mask, epoch."""
@@ -167,11 +154,6 @@ class OverAggregate:
             out.append((int(a["key"][i]), int(a["rowtime"][i]), int(a["ordinal"][i]), v))
         return out
 
-    def stats(self):
-        s = N.FwOverStats()
-        self._check(N.lib().fw_over_get_stats(self._h, ctypes.byref(s)))
-        return {f: getattr(s, f) for f, _ in N.FwOverStats._fields_}
-
     def snapshot(self, kg):
         """The keyed state of key group kg: {"key", "last_ts", "acc" [keys, words], "n_rows", "ts", "ordinal",
         "cols" [rows, columns], "nulls"} (numpy)."""
@@ -193,14 +175,3 @@ class OverAggregate:
               for f, _ in N.FwOverState._fields_}
         src = N.FwOverState(*(st[f].ctypes.data for f, _ in N.FwOverState._fields_))
         self._check(N.lib().fw_over_restore_key_group(self._h, kg, ctypes.byref(src), len(st["key"]), len(st["ts"])))
-
-    def close(self):
-        if self._h:
-            N.lib().fw_over_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

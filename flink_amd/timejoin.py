@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from ._handle import _TableHandle
 
 _KEY_KINDS = {"long": N.FW_KEY_LONG, "int": N.FW_KEY_INT, "hashed": N.FW_KEY_HASHED}
 JOIN_TYPES = {"inner": N.FW_TJOIN_INNER, "left": N.FW_TJOIN_LEFT, "right": N.FW_TJOIN_RIGHT, "full": N.FW_TJOIN_FULL}
@@ -33,25 +34,16 @@ def tjoin_config(join_type, lower, upper, allowed_lateness=0, key_type="long", m
     return c
 
 
-class TimeBoundedJoin:
+class TimeBoundedJoin(_TableHandle):
     """One keyed row-time interval join.  join_type: "inner", "left", "right" or "full"; lower / upper: the bounds of
     l.rowtime - r.rowtime in ms.  process(side, keys, rowtimes[, vals, key_hash]) takes numpy arrays or CUDA tensors,
     side[i] 0 = left / 1 = right, index order = arrival order; watermark(wm) returns (rows, forwarded watermark), the
     rows emitted since the last call as a TJOIN_ROW_DTYPE array."""
+    _prefix, _Rows, _Stats = "fw_tjoin", N.FwTjoinRows, N.FwTjoinStats
 
     def __init__(self, join_type, lower, upper, allowed_lateness=0, key_type="long", **kw):
         cfg = tjoin_config(join_type, lower, upper, allowed_lateness, key_type=key_type, **kw)
-        self._h = ctypes.c_void_p()
-        rc = N.lib().fw_tjoin_create(ctypes.byref(cfg), ctypes.byref(self._h))
-        if rc != N.FW_OK:
-            msg = N.lib().fw_tjoin_last_error(self._h).decode() if self._h else "error"
-            N.lib().fw_tjoin_destroy(self._h)
-            self._h = None
-            raise N.NativeError(rc, msg)
-
-    def _check(self, rc):
-        if rc != N.FW_OK:
-            raise N.NativeError(rc, N.lib().fw_tjoin_last_error(self._h).decode())
+        self._create(cfg)
 
     def process(self, side, keys, rowtimes, vals=None, key_hash=None):
         L = N.lib()
@@ -105,12 +97,7 @@ class TimeBoundedJoin:
     def rows_device(self):
         """The pending output rows where they are, in HBM: (FwTjoinRows of device pointers, rows).  Valid until the
         next call on the handle; the rows stay pending (clear_pending() discards them)."""
-        rows, n = N.FwTjoinRows(), ctypes.c_int64()
-        self._check(N.lib().fw_tjoin_rows_device(self._h, ctypes.byref(rows), ctypes.byref(n)))
-        return rows, n.value
-
-    def clear_pending(self):
-        self._check(N.lib().fw_tjoin_clear_pending(self._h))
+        return self._rows_device()
 
     def drain(self):
         """The pending output rows (TJOIN_ROW_DTYPE), removed from the handle."""
@@ -128,11 +115,6 @@ class TimeBoundedJoin:
     def watermark(self, wm):
         _, fw = self.advance_watermark(wm)
         return self.drain(), fw
-
-    def stats(self):
-        s = N.FwTjoinStats()
-        self._check(N.lib().fw_tjoin_get_stats(self._h, ctypes.byref(s)))
-        return {f: getattr(s, f) for f, _ in N.FwTjoinStats._fields_}
 
     def snapshot(self, kg):
         """The keyed state of key group kg: {"key", "left_timer", "right_timer", "n_rows"} per key and {"side",
@@ -154,14 +136,3 @@ class TimeBoundedJoin:
         src = N.FwTjoinState(*(st[f].ctypes.data for f, _ in N.FwTjoinState._fields_))
         self._check(N.lib().fw_tjoin_restore_key_group(self._h, kg, ctypes.byref(src), len(st["key"]),
                                                        len(st["rowtime"])))
-
-    def close(self):
-        if self._h:
-            N.lib().fw_tjoin_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

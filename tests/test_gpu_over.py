@@ -451,3 +451,47 @@ def test_gpu_over_device_view_and_clear_pending():
     assert len(ga["key"]) > 0 and (ga["epoch"] == 2).all()  # only the third watermark call's rows, tagged as such
     a.close()
     b.close()
+
+
+def _drain_some(op, cap):
+    """fw_over_drain with room for `cap` rows: the rows it hands out (drain_arrays' fields)"""
+    import ctypes
+    ns = len(op.aggregates)
+    out = {"key": np.full(cap, -7, np.int64), "rowtime": np.full(cap, -7, np.int64), "ordinal": np.full(cap, -7, np.int64),
+           "values": np.full((cap, ns), -7, np.int64), "null_mask": np.full(cap, 7, np.uint32),
+           "epoch": np.full(cap, -7, np.int64)}
+    dst = N.FwOverRows(*(out[f].ctypes.data for f in ("key", "rowtime", "ordinal", "values", "null_mask")))
+    got = ctypes.c_int64()
+    op._check(N.lib().fw_over_drain(op._h, ctypes.byref(dst), out["epoch"].ctypes.data, cap, ctypes.byref(got)))
+    assert 0 <= got.value <= cap
+    return {f: a[:got.value] for f, a in out.items()}
+
+
+def test_gpu_over_partial_drains_hand_out_the_rows_and_epochs_of_one_drain():
+    """Three drains (less than the first watermark's rows, to the middle of the second's, the rest) return what one
+    drain returns, epochs included.  13 rows of three keys fire in watermark calls of 4, 5 and 4 rows; three aggregates,
+    so a row of `values` is wider than the other columns, and two rows whose SUM is NULL."""
+    keys = np.array([5, -3, 9] * 4 + [5], np.int64)
+    ts = np.arange(1, 14, dtype=np.int64)
+    col = np.arange(100, 113, dtype=np.int64)
+    nulls = np.zeros(13, np.uint8)
+    nulls[[0, 3]] = 1  # key 5's first two rows
+    aggs = [("sum", 0), ("count_star", 0), ("max", 0)]
+    a, b = gpu_op("bounded_rows", 1, ["long"], aggs), gpu_op("bounded_rows", 1, ["long"], aggs)
+    for op in (a, b):
+        op.process(keys, ts, [col], nulls)
+        assert [op.advance_watermark(wm) for wm in (4, 9, 13)] == [4, 5, 4]
+    one = b.drain_arrays()
+    assert one["epoch"].tolist() == [0] * 4 + [1] * 5 + [2] * 4
+    assert sorted(one["rowtime"].tolist()) == ts.tolist() and np.count_nonzero(one["null_mask"]) == 2
+    assert a.stats()["pending_output_rows"] == 13
+    parts = []
+    for cap, left in ((3, 10), (4, 6), (100, 0)):
+        parts.append(_drain_some(a, cap))
+        assert a.stats()["pending_output_rows"] == left
+    assert [len(p["key"]) for p in parts] == [3, 4, 6]
+    for f in one:
+        assert np.array_equal(np.concatenate([p[f] for p in parts]), one[f]), f
+    assert len(_drain_some(a, 5)["key"]) == 0 and len(b.drain_arrays()["key"]) == 0
+    a.close()
+    b.close()

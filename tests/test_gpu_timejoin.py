@@ -442,3 +442,60 @@ def test_rows_device_then_clear_pending_equals_drain():
     assert a.op.stats()["pending_output_rows"] == 0 and len(a.op.drain()) == 0
     for e in (a, b):
         e.op.close()
+
+
+def _drain_some(op, cap):
+    """fw_tjoin_drain with room for `cap` rows: the rows it hands out (TJOIN_ROW_DTYPE fields as lists)"""
+    import ctypes
+    fields = [f for f, _ in N.FwTjoinRows._fields_]
+    cols = {f: np.full(cap, -7, np.int64) for f in fields + ["epoch"]}
+    dst = N.FwTjoinRows(*(cols[f].ctypes.data for f in fields))
+    got = ctypes.c_int64()
+    op._check(N.lib().fw_tjoin_drain(op._h, ctypes.byref(dst), cols["epoch"].ctypes.data, cap, ctypes.byref(got)))
+    assert 0 <= got.value <= cap
+    return {f: cols[f][:got.value].tolist() for f in cols}
+
+
+def test_partial_drains_hand_out_the_rows_and_epochs_of_one_drain():
+    """Three drains (less than the first call's rows, to the middle of the second call's, the rest) return what one
+    drain returns, epochs included.  A full join: pushes append pairs and arrival padding, watermarks timer padding,
+    four rows per watermark call.  Every push brings at most one new key, so both handles number the key slots alike
+    and emit in the same order."""
+    steps = [("p", [(0, 1, 100, 11)]),
+             ("p", [(1, 1, 105, 12), (0, 2, 100, 21)]),
+             ("p", [(1, 2, 95, 22), (1, 1, 108, 13), (0, 3, 100, 31)]),
+             ("w", 121),
+             ("p", [(0, 1, 200, 14), (0, 4, 200, 41), (0, 3, 201, 32)]),
+             ("p", [(1, 1, 195, 15), (1, 4, 205, 42), (1, 2, 50, 23)]),
+             ("w", 222),
+             ("p", [(0, 2, 300, 24), (1, 3, 300, 33), (0, 4, 301, 43)]),
+             ("p", [(1, 2, 305, 25), (1, 2, 295, 26)]),
+             ("w", 322)]
+    a, b, ref = TimeBoundedJoin("full", -10, 10), TimeBoundedJoin("full", -10, 10), RefEngine("full", -10, 10)
+    exp_rows, from_timers = [], 0
+    for kind, arg in steps:
+        if kind == "p":
+            cols = [list(c) for c in zip(*arg)]
+            exp_rows += ref.push(*cols)
+            for op in (a, b):
+                op.process(*cols)
+        else:
+            rows, _ = ref.watermark(arg)
+            exp_rows += rows
+            from_timers += len(rows)
+            for op in (a, b):
+                op.advance_watermark(arg)
+    one = b.drain()
+    assert one["epoch"].tolist() == [0] * 4 + [1] * 4 + [2] * 4 and from_timers == 4
+    assert sorted(rows_as_tuples(one)) == sorted(exp_rows)
+    assert a.stats()["pending_output_rows"] == 12
+    parts = []
+    for cap, left in ((3, 9), (3, 6), (100, 0)):
+        parts.append(_drain_some(a, cap))
+        assert a.stats()["pending_output_rows"] == left
+    assert [len(p["key"]) for p in parts] == [3, 3, 6]
+    for f in one.dtype.names:
+        assert sum((p[f] for p in parts), []) == one[f].tolist(), f
+    assert _drain_some(a, 5)["key"] == [] and len(b.drain()) == 0
+    a.close()
+    b.close()
