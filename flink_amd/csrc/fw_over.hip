@@ -59,8 +59,14 @@ struct ORowsD {  // the row store, or a watermark's gathered rows: columns of `c
   int64_t cap;
 };
 
-// Double.compare order as a signed integer order, and back (its own inverse)
-__host__ __device__ inline int64_t f64_key(int64_t b) { return b ^ (int64_t)((uint64_t)(b >> 63) >> 1); }
+// Double.compare order as a signed integer order (every NaN the canonical one, Double.doubleToLongBits), and back
+__host__ __device__ inline int64_t f64_unkey(int64_t k) { return k ^ (int64_t)((uint64_t)(k >> 63) >> 1); }
+__host__ __device__ inline int64_t f64_key(int64_t b) {
+  if ((b & 0x7ff0000000000000ll) == 0x7ff0000000000000ll && (b & 0x000fffffffffffffll)) b = 0x7ff8000000000000ll;
+  return f64_unkey(b);
+}
+__device__ __forceinline__ bool f64_finite(int64_t b) { return (b & 0x7ff0000000000000ll) != 0x7ff0000000000000ll; }
+__device__ __forceinline__ bool f64_nan(int64_t b) { return !f64_finite(b) && (b & 0x000fffffffffffffll); }
 __host__ __device__ inline bool ov_float(int t) { return t == FW_VAL_F64 || t == FW_VAL_F32; }
 __host__ __device__ inline int64_t ov_narrow(int t, int64_t v) {
   return t == FW_VAL_I32 ? (int64_t)(int32_t)v : t == FW_VAL_I16 ? (int64_t)(int16_t)v
@@ -243,7 +249,7 @@ __device__ __forceinline__ int64_t last_true_up(int64_t a, int64_t b, P pred) {
 // per gathered row: its frame [lo, hi] in the sorted rows, whether it fires, whether some later frame can reach it
 __global__ __launch_bounds__(256) void k_ov_frames(OCfg c, OMap mp, ORowsD g, int64_t m, uint32_t* __restrict__ flo,
                                                    uint32_t* __restrict__ fhi, uint32_t* __restrict__ fire,
-                                                   uint32_t* __restrict__ keep) {
+                                                   uint32_t* __restrict__ keep, uint32_t* __restrict__ fseg) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
   const uint32_t s = g.slot[i];
@@ -269,11 +275,13 @@ __global__ __launch_bounds__(256) void k_ov_frames(OCfg c, OMap mp, ORowsD g, in
   fhi[i] = (uint32_t)hi;
   fire[i] = fr ? 1u : 0u;
   keep[i] = kp ? 1u : 0u;
+  if (fseg) fseg[i] = (uint32_t)seg0;
 }
 
 // ---------------------------------------------------------------- watermark: segmented scans
 // the scan's element: a column's non-null count and sum over the rows since the run's start ("f": a run starts in
-// here).  Integral sums are 128-bit two's complement (lo, hi) and wrap; a Double sum is the f64 in lo.
+// here).  Integral sums are 128-bit two's complement (lo, hi) and wrap; a Double sum is the f64 in lo, and hi counts
+// the column's +Inf values (low 32 bits) and -Inf values (high 32 bits).
 struct SAcc {
   unsigned long long nn, lo;
   long long hi;
@@ -285,6 +293,7 @@ __device__ __forceinline__ void sacc_add(SAcc& a, const SAcc& b) {  // a = a + b
   if (F64) {
     a.lo = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)a.lo) +
                                                     __longlong_as_double((long long)b.lo));
+    a.hi = (long long)((unsigned long long)a.hi + (unsigned long long)b.hi);
   } else {
     const unsigned long long l = a.lo + b.lo;
     a.hi = (long long)((unsigned long long)a.hi + (unsigned long long)b.hi + (l < a.lo ? 1ull : 0ull));
@@ -351,7 +360,13 @@ __global__ __launch_bounds__(OV_THREADS) void k_ov_scan_tile(ORowsD g, int j, in
         const int64_t x = g.cols[(int64_t)j * g.cap + i];
         e.nn = 1;
         e.lo = (unsigned long long)x;
-        e.hi = F64 ? 0 : (x < 0 ? -1ll : 0ll);
+        e.hi = x < 0 ? -1ll : 0ll;
+        if (F64) {
+          // SumWithRetractAggFunction.scala:43-60 starts from +0.0, so its sum is never -0.0: neither is an element
+          const double d = __longlong_as_double(x);
+          e.lo = (unsigned long long)__double_as_longlong(0.0 + d);
+          e.hi = d == __builtin_inf() ? 1ll : d == -__builtin_inf() ? (1ll << 32) : 0ll;
+        }
       }
       if (e.f && myfirst == 0xffffffffu) myfirst = (uint32_t)i;
     }
@@ -388,7 +403,7 @@ __global__ __launch_bounds__(OV_THREADS) void k_ov_scan_tile(ORowsD g, int j, in
     }
     pnn[i] = o.nn;
     plo[i] = o.lo;
-    if (!F64) phi[i] = o.hi;
+    phi[i] = o.hi;
   }
   if (threadIdx.x == OV_THREADS - 1) tagg[blockIdx.x] = inc;
   if (threadIdx.x == 0) thead[blockIdx.x] = first;  // (read after the atomics: ordered by the barriers above)
@@ -505,10 +520,15 @@ struct OScan {  // per column: the tiles' scans and carries (null for a column n
   const SAcc* carry[8];
   const uint32_t* thead;
   ORmq mn[8], mx[8];  // base == null: none
+  // bounded kinds, per Double column with a SUM / AVG: the rows where the key's sum turns non-finite (flags and their
+  // exclusive scan), and every row's run start (null: none)
+  const uint32_t* bad[8];
+  const uint32_t* bcnt[8];
+  const uint32_t* fseg;
 };
 // the scanned value at row i: the tile's own scan plus, before the tile's first run start, the carry
 __device__ __forceinline__ SAcc scan_at(const OScan& sc, int j, bool f64, int64_t i) {
-  SAcc a{sc.pnn[j][i], sc.plo[j][i], f64 ? 0 : sc.phi[j][i], 0};
+  SAcc a{sc.pnn[j][i], sc.plo[j][i], sc.phi[j][i], 0};
   const int64_t t = i / OV_TILE;
   if ((uint32_t)i < sc.thead[t]) {
     SAcc c = sc.carry[j][t];
@@ -527,6 +547,7 @@ __device__ __forceinline__ SAcc frame_col(const OScan& sc, const ORowsD& g, int 
     if (f64) {
       a.lo = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)a.lo) -
                                                       __longlong_as_double((long long)b.lo));
+      a.hi = (long long)((unsigned long long)a.hi - (unsigned long long)b.hi);
     } else {
       const unsigned long long l = a.lo - b.lo;
       a.hi = (long long)((unsigned long long)a.hi - (unsigned long long)b.hi - (a.lo < b.lo ? 1ull : 0ull));
@@ -535,6 +556,50 @@ __device__ __forceinline__ SAcc frame_col(const OScan& sc, const ORowsD& g, int 
   }
   return a;
 }
+// ---- bounded kinds, Double SUM / AVG: the sum that is not finite.  The reference keeps one accumulator per key, adds
+// the rows entering the frame and subtracts the rows leaving it (SumWithRetractAggFunction.scala:43-60), so a sum that
+// is NaN or infinite once is never finite again for the key: +Inf stays until a -Inf or a NaN is added or a +Inf is
+// subtracted (NaN from then on), -Inf likewise.  Up to the first such row of a key a frame's prefix difference is the
+// reference's value; from it on the value is that row's (or, across watermarks, the key's carried one: the sum word
+// of the slot's accumulator, 0 while the last emitted sum was finite) unless one of those events lies between.
+__device__ __forceinline__ int64_t* ov_carry(const OCfg& c, const OMap& mp, uint32_t slot, int j) {
+  return mp.sacc + (int64_t)slot * ov_accw(c) + 2 + 5 * j;
+}
+// flags: a firing row whose frame's sum is not finite; the key's last fired row when the key carries such a sum
+__global__ __launch_bounds__(256) void k_ov_nonfinite(OCfg c, OMap mp, OScan sc, ORowsD g, int j, int64_t m,
+                                                      const uint32_t* __restrict__ flo, const uint32_t* __restrict__ fhi,
+                                                      const uint32_t* __restrict__ fire, uint32_t* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  bool b;
+  if (fire[i]) b = !f64_finite((int64_t)frame_col(sc, g, j, true, flo[i], fhi[i]).lo);
+  else b = i + 1 < m && fire[i + 1] && g.slot[i + 1] == g.slot[i] && !f64_finite(*ov_carry(c, mp, g.slot[i], j));
+  bad[i] = b ? 1u : 0u;
+}
+// the sum of firing row i's frame, `sum` its prefix difference
+__device__ int64_t ov_sticky_sum(const OCfg& c, const OMap& mp, const OScan& sc, const ORowsD& g, int j, int64_t i,
+                                 const uint32_t* flo, const uint32_t* fhi, const uint32_t* fire, int64_t sum) {
+  const uint32_t *bad = sc.bad[j], *cnt = sc.bcnt[j];
+  const int64_t seg0 = sc.fseg[i];
+  const uint32_t base = cnt[seg0];
+  if (cnt[i] + bad[i] == base) return sum;  // finite so far
+  const int64_t e = first_true_down(seg0, i, [&](int64_t x) { return cnt[x] + bad[x] != base; });
+  if (e == i) return sum;                   // the first one
+  const int64_t s0 = fire[e] ? (int64_t)frame_col(sc, g, j, true, flo[e], fhi[e]).lo : *ov_carry(c, mp, g.slot[e], j);
+  if (f64_nan(s0)) return s0;
+  // since row e: the infinities added (the rows behind e's frame end up to i's) and subtracted (the rows from e's
+  // frame start to before i's), {+Inf, -Inf} counts packed as in the scan
+  const SAcc ph = scan_at(sc, j, true, fhi[i]);
+  const unsigned long long added = (unsigned long long)ph.hi - (unsigned long long)scan_at(sc, j, true, fhi[e]).hi;
+  const int64_t li = flo[i], le = flo[e];
+  const unsigned long long gone = (li > seg0 ? (unsigned long long)scan_at(sc, j, true, li - 1).hi : 0ull) -
+                                  (le > seg0 ? (unsigned long long)scan_at(sc, j, true, le - 1).hi : 0ull);
+  const bool pos = s0 > 0;  // (the bits of +Inf)
+  const bool broken = f64_nan((int64_t)ph.lo) || (pos ? (added >> 32) != 0 || (uint32_t)gone != 0
+                                                      : (uint32_t)added != 0 || (gone >> 32) != 0);
+  return broken ? 0x7ff8000000000000ll : s0;
+}
+
 // |x| / d of a 128-bit two's-complement x (d >= 1) toward zero (BigInteger.divide, AvgAggFunction.scala:160-166)
 __device__ int64_t ov_div128(unsigned long long lo, long long hi, unsigned long long d) {
   const bool neg = hi < 0;
@@ -607,7 +672,9 @@ __global__ __launch_bounds__(256) void k_ov_eval(OCfg c, OMap mp, OScan sc, ORow
       v = hi - lo + 1 + (acc ? acc[0] : 0);
     } else {
       const int t = c.ctype[j];
-      const OCol o = ov_col(c, sc, g, acc, j, lo, hi, fn == FW_ROW_MIN, fn == FW_ROW_MAX);
+      OCol o = ov_col(c, sc, g, acc, j, lo, hi, fn == FW_ROW_MIN, fn == FW_ROW_MAX);
+      if (sc.bad[j] && (fn == FW_ROW_SUM || fn == FW_ROW_AVG))
+        o.s.lo = (unsigned long long)ov_sticky_sum(c, mp, sc, g, j, i, flo, fhi, fire, (int64_t)o.s.lo);
       if (fn == FW_ROW_COUNT) {
         v = (int64_t)o.s.nn;
       } else if (o.s.nn == 0) {
@@ -615,9 +682,9 @@ __global__ __launch_bounds__(256) void k_ov_eval(OCfg c, OMap mp, OScan sc, ORow
       } else if (fn == FW_ROW_SUM) {
         v = ov_float(t) ? (int64_t)o.s.lo : ov_narrow(t, (int64_t)o.s.lo);
       } else if (fn == FW_ROW_MIN) {
-        v = ov_float(t) ? f64_key(o.mn) : o.mn;
+        v = ov_float(t) ? f64_unkey(o.mn) : o.mn;
       } else if (fn == FW_ROW_MAX) {
-        v = ov_float(t) ? f64_key(o.mx) : o.mx;
+        v = ov_float(t) ? f64_unkey(o.mx) : o.mx;
       } else {  // FW_ROW_AVG
         if (ov_float(t)) v = __double_as_longlong(__longlong_as_double((long long)o.s.lo) / (double)o.s.nn);
         else if (t == FW_VAL_I64) v = ov_div128(o.s.lo, o.s.hi, o.s.nn);
@@ -630,13 +697,19 @@ __global__ __launch_bounds__(256) void k_ov_eval(OCfg c, OMap mp, OScan sc, ORow
 }
 // the keys' new state, by the thread of each run's last row (one per key; the evaluation has read the old state)
 __global__ __launch_bounds__(256) void k_ov_state(OCfg c, OMap mp, OScan sc, ORowsD g, int64_t m, const uint32_t* __restrict__ flo,
-                                                  const uint32_t* __restrict__ fire, uint32_t used_cols) {
+                                                  const uint32_t* __restrict__ fhi, const uint32_t* __restrict__ fire,
+                                                  uint32_t used_cols) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m || !fire[i]) return;
   const uint32_t slot = g.slot[i];
   if (i + 1 < m && g.slot[i + 1] == slot) return;
   if (ov_bounded(c)) {
     mp.slast[slot] = g.ts[i];
+    for (int j = 0; j < c.nc; j++) {  // the last emitted Double sum, kept while it is not finite
+      if (!sc.bad[j]) continue;
+      const int64_t s = ov_sticky_sum(c, mp, sc, g, j, i, flo, fhi, fire, (int64_t)frame_col(sc, g, j, true, flo[i], fhi[i]).lo);
+      *ov_carry(c, mp, slot, j) = f64_finite(s) ? 0 : s;
+    }
     return;
   }
   int64_t* acc = mp.sacc + (int64_t)slot * ov_accw(c);
@@ -648,9 +721,9 @@ __global__ __launch_bounds__(256) void k_ov_state(OCfg c, OMap mp, OScan sc, ORo
     int64_t* a = acc + 1 + 5 * j;
     a[0] = (int64_t)o.s.nn;
     a[1] = (int64_t)o.s.lo;
-    a[2] = f64 ? 0 : o.s.hi;
-    a[3] = o.s.nn && sc.mn[j].base ? (f64 ? f64_key(o.mn) : o.mn) : 0;
-    a[4] = o.s.nn && sc.mx[j].base ? (f64 ? f64_key(o.mx) : o.mx) : 0;
+    a[2] = f64 ? 0 : o.s.hi;  // (a Double's Inf counts are a run's own)
+    a[3] = o.s.nn && sc.mn[j].base ? (f64 ? f64_unkey(o.mn) : o.mn) : 0;
+    a[4] = o.s.nn && sc.mx[j].base ? (f64 ? f64_unkey(o.mx) : o.mx) : 0;
   }
   acc[0] = jadd(acc[0], i - lo + 1);
 }
@@ -716,8 +789,8 @@ __global__ __launch_bounds__(256) void k_ov_restore_keys(OCfg c, OMap m, OCtr* c
   const int32_t slot = keymap_claim(m, &ctr->nslots, &ctr->map_full, key[i], [&] { return kg; });
   if (slot < 0) return;
   m.slast[slot] = ov_bounded(c) ? last[i] : 0;
-  const int w = ov_accw(c);
-  for (int q = 0; q < w; q++) m.sacc[(int64_t)slot * w + q] = ov_bounded(c) ? 0 : acc[i * w + q];
+  const int w = ov_accw(c);  // (a bounded key's words: zero but for a carried non-finite Double sum)
+  for (int q = 0; q < w; q++) m.sacc[(int64_t)slot * w + q] = acc[i * w + q];
 }
 __global__ __launch_bounds__(256) void k_ov_restore_rows(OCfg c, OMap m, ORowsD st, int64_t base, const int64_t* __restrict__ key,
                                                          const int64_t* __restrict__ ts, const int64_t* __restrict__ ord,
@@ -758,6 +831,8 @@ struct fw_over : TableHandle {  // (oseg's epochs: the watermark calls)
   int64_t wm_calls = 0;
   OOut out{};
   uint32_t used_cols = 0, min_cols = 0, max_cols = 0;
+  uint32_t fsum_cols = 0;    // bounded kinds: the Double columns with a SUM / AVG
+  Buf b_fseg, b_bad[8], b_bcnt[8];
   Buf b_stage[5], b_pslot, b_pkeep, b_ppos, b_sel, b_pos, b_sk[2], b_sv[2], b_k2[2];
   Buf b_g[5], b_flo, b_fhi, b_fire, b_keep, b_opos, b_kpos, b_thead;
   Buf b_pnn[8], b_plo[8], b_phi[8], b_tagg[8], b_carry[8];
@@ -894,7 +969,9 @@ int do_watermark(fw_over* op, int64_t wm, int64_t* n_rows) {
     return rc;
   uint32_t *flo = (uint32_t*)op->b_flo.p, *fhi = (uint32_t*)op->b_fhi.p, *fire = (uint32_t*)op->b_fire.p,
            *keep = (uint32_t*)op->b_keep.p, *opos = (uint32_t*)op->b_opos.p, *kpos = (uint32_t*)op->b_kpos.p;
-  hipLaunchKernelGGL(k_ov_frames, dim3(grid_of(m)), dim3(256), 0, op->stream, c, op->map, g, m, flo, fhi, fire, keep);
+  if (op->fsum_cols && (rc = ensure(op, op->b_fseg, (size_t)m * 4))) return rc;
+  hipLaunchKernelGGL(k_ov_frames, dim3(grid_of(m)), dim3(256), 0, op->stream, c, op->map, g, m, flo, fhi, fire, keep,
+                     op->fsum_cols ? (uint32_t*)op->b_fseg.p : nullptr);
   if ((rc = excl_scan(op, fire, opos, m)) || (rc = excl_scan(op, keep, kpos, m))) return rc;
   hipLaunchKernelGGL(k_ov_total, dim3(1), dim3(1), 0, op->stream, fire, opos, m, op->tot);
   hipLaunchKernelGGL(k_ov_total, dim3(1), dim3(1), 0, op->stream, keep, kpos, m, op->tot + 1);
@@ -940,13 +1017,26 @@ int do_watermark(fw_over* op, int64_t wm, int64_t* n_rows) {
       (is_max ? sc.mx[j] : sc.mn[j]) = r;
     }
   }
+  for (int j = 0; j < c.nc; j++) {  // where a bounded key's Double sum stops being finite (after every scan)
+    if (!((op->fsum_cols >> j) & 1)) continue;
+    if ((rc = ensure(op, op->b_bad[j], (size_t)m * 4)) || (rc = ensure(op, op->b_bcnt[j], (size_t)m * 4))) return rc;
+    hipLaunchKernelGGL(k_ov_nonfinite, dim3(grid_of(m)), dim3(256), 0, op->stream, c, op->map, sc, g, j, m,
+                       (const uint32_t*)flo, (const uint32_t*)fhi, (const uint32_t*)fire, (uint32_t*)op->b_bad[j].p);
+    if ((rc = excl_scan(op, (const uint32_t*)op->b_bad[j].p, (uint32_t*)op->b_bcnt[j].p, m))) return rc;
+  }
+  for (int j = 0; j < c.nc; j++) {
+    if (!((op->fsum_cols >> j) & 1)) continue;
+    sc.bad[j] = (const uint32_t*)op->b_bad[j].p;
+    sc.bcnt[j] = (const uint32_t*)op->b_bcnt[j].p;
+    sc.fseg = (const uint32_t*)op->b_fseg.p;
+  }
   TB_HIP(op, hipMemcpyAsync(htot, op->tot, 16, hipMemcpyDeviceToHost, op->stream));
   TB_HIP(op, hipStreamSynchronize(op->stream));
   const int64_t nfire = (int64_t)htot[0], nkeep = (int64_t)htot[1];
   if ((rc = grow_out(op, op->n_out + nfire))) return rc;  // the row buffer, from the exact count
   hipLaunchKernelGGL(k_ov_eval, dim3(grid_of(m)), dim3(256), 0, op->stream, c, op->map, sc, g, m, flo, fhi, fire, opos,
                      op->n_out, op->ocap, op->out.key, op->out.ts, op->out.ord, op->out.val, op->out.nul);
-  hipLaunchKernelGGL(k_ov_state, dim3(grid_of(m)), dim3(256), 0, op->stream, c, op->map, sc, g, m, flo, fire, op->used_cols);
+  hipLaunchKernelGGL(k_ov_state, dim3(grid_of(m)), dim3(256), 0, op->stream, c, op->map, sc, g, m, flo, fhi, fire, op->used_cols);
   hipLaunchKernelGGL(k_ov_retain, dim3(grid_of(m)), dim3(256), 0, op->stream, c, g, other, m, rest, keep, kpos);
   if ((rc = read_ctr(op))) return rc;
   TB_HIP(op, hipGetLastError());
@@ -1024,6 +1114,7 @@ int fw_over_create(const fw_over_config* cfg, fw_over** out) {
     op->used_cols |= 1u << j;
     if (fn == FW_ROW_MIN) op->min_cols |= 1u << j;
     if (fn == FW_ROW_MAX) op->max_cols |= 1u << j;
+    if ((fn == FW_ROW_SUM || fn == FW_ROW_AVG) && ov_bounded(d) && d.ctype[j] == FW_VAL_F64) op->fsum_cols |= 1u << j;
   }
   *out = op;
   // ---- the GPU from here on

@@ -992,8 +992,10 @@ typedef struct fw_over_stats {
 
 /* keyed state of one key group.  Per key: last_ts = lastTriggeringTs (bounded kinds; 0 otherwise), acc = the unbounded
  * kinds' accumulator Row as FW_OVER_ACC_WORDS(row_columns) words: the rows accumulated, then per column its non-null
- * count, the sum's low and high words (Double: the f64 sum, 0), min and max (0 when the count is 0); zeros for the
- * bounded kinds, whose accumulators are functions of the retained rows.  n_rows[i] rows of key i follow each other in
+ * count, the sum's low and high words (Double: the f64 sum, 0), min and max (0 when the count is 0).  The
+ * bounded kinds' accumulators are functions of the retained rows: their words are zero, but for the sum word of a
+ * Double column with a SUM / AVG while the key's last emitted sum is NaN or infinite (it holds that sum, which the
+ * reference's retracting accumulator never loses again); a snapshot of all zeros restores as it always did.  n_rows[i] rows of key i follow each other in
  * the row columns (retained and pending rows in arrival order): cols[r * row_columns + j], nulls[r] bit j. */
 #define FW_OVER_ACC_WORDS(columns) (1 + 5 * (columns))
 typedef struct fw_over_state {

@@ -11,6 +11,7 @@ lastTriggeringTs (an unset ValueState[Long] reads as 0).  Plain Python, independ
 Idle-state retention (the processing-time clean-up timers) is not restated: the default StreamQueryConfig has none.
 """
 import math
+import struct
 
 LMIN, LMAX = -(1 << 63), (1 << 63) - 1
 _BITS = {"long": 64, "int": 32, "short": 16, "byte": 8}
@@ -26,15 +27,58 @@ def _tdiv(s, c):
     return -q if s < 0 else q
 
 
-class _Agg:
-    """One built-in aggregate with retraction (functions/aggfunctions/*WithRetractAggFunction.scala, CountAggFunction,
-    AvgAggFunction): getValue is None (SQL NULL) while no non-null value is accumulated, except for the counts."""
+NAN_BITS = 0x7FF8000000000000
 
-    def __init__(self, fn, typ):
-        self.fn, self.typ = fn, typ
+
+def double_bits(v):
+    """Double.doubleToLongBits: the signed 64 bits, every NaN the canonical one"""
+    return NAN_BITS if v != v else struct.unpack("<q", struct.pack("<d", v))[0]
+
+
+def _compare(a, b):
+    """ord.compare: Ordering.Double.compare is java.lang.Double.compare (Scala 2.11.12) -- numeric order, then the
+    doubleToLongBits, so -0.0 < 0.0 and NaN == NaN is above +Inf; Ordering.Long etc. are the plain order"""
+    if a < b:
+        return -1
+    if a > b:
+        return 1
+    if isinstance(a, float) or isinstance(b, float):
+        x, y = double_bits(a), double_bits(b)
+        return (x > y) - (x < y)
+    return 0
+
+
+class _Agg:
+    """One built-in aggregate (functions/aggfunctions/): getValue is None (SQL NULL) while no non-null value is
+    accumulated, except for the counts.
+
+    Bounded kinds get the retracting functions, unbounded kinds the plain ones (AggregateUtil.scala:230-236
+    `needRetract = true` in createBoundedOverProcessFunction, :86-91 `needRetraction = false` in
+    createUnboundedOverProcessFunction; the choice itself at :1158-1347).
+
+    MIN / MAX with retraction (MinAggFunctionWithRetract.scala:50-100, MaxAggFunctionWithRetract.scala:50-100), line
+    for line: a HashMap value -> count whose keys are boxed values (Double.equals / hashCode: by doubleToLongBits,
+    NaN canonical, -0.0 != 0.0), the current extreme f0 chosen by ord.compare, `v == acc.f0` on retraction (boxed
+    `==`: numeric equality, false for NaN, true for -0.0 against 0.0), f0 back to the initial value when the map
+    empties.  So a MAX whose NaN leaves while other values remain keeps the NaN: it is not rescanned.
+    MIN / MAX without retraction (MinAggFunction.scala / MaxAggFunction.scala:49-57): f0 and a flag, ord.compare.
+
+    SUM / AVG: plain sequential `+` and `-` from +0.0 / 0 (SumWithRetractAggFunction.scala:43-60, SumAggFunction.scala
+    :39-53, AvgAggFunction.scala:214-242), so a sum of only -0.0 is +0.0, a retracted infinity leaves Inf - Inf = NaN
+    and a non-finite sum never becomes finite again."""
+
+    def __init__(self, fn, typ, retract=True):
+        self.fn, self.typ, self.retracting = fn, typ, retract
         self.count = 0
-        self.sum = 0.0 if typ in ("double", "float") else 0
-        self.values = []
+        self.floating = typ in ("double", "float")
+        self.sum = 0.0 if self.floating else 0
+        self.f0 = self.init = 0.0 if self.floating else 0   # getInitValue
+        self.map = {}                                       # key -> [the boxed value, its count]
+        self.f1 = False
+        self.sign = -1 if fn == "max" else 1                # MAX: ord.compare(f0, v) < 0; MIN: > 0
+
+    def _key(self, v):
+        return double_bits(v) if self.floating else v
 
     def accumulate(self, v):
         if self.fn == "count_star":
@@ -44,7 +88,18 @@ class _Agg:
             return
         self.count += 1
         if self.fn in ("min", "max"):
-            self.values.append(v)
+            if not self.retracting:
+                if not self.f1 or _compare(self.f0, v) * self.sign > 0:
+                    self.f0 = v
+                    self.f1 = True
+                return
+            if len(self.map) == 0 or _compare(self.f0, v) * self.sign > 0:
+                self.f0 = v
+            k = self._key(v)
+            if k not in self.map:
+                self.map[k] = [v, 1]
+            else:
+                self.map[k][1] += 1
         elif self.fn in ("sum", "avg"):
             self.sum = self.sum + v
             if self.typ in _BITS:
@@ -54,6 +109,7 @@ class _Agg:
                     self.sum = _wrap(self.sum, bits)
 
     def retract(self, v):
+        assert self.retracting
         if self.fn == "count_star":
             self.count -= 1
             return
@@ -61,7 +117,21 @@ class _Agg:
             return
         self.count -= 1
         if self.fn in ("min", "max"):
-            self.values.remove(v)
+            k = self._key(v)
+            count = self.map[k][1] - 1
+            if count == 0:
+                del self.map[k]
+                if len(self.map) == 0:
+                    self.f0 = self.init
+                    return
+                if v == self.f0:                            # numeric: never true for NaN
+                    it = iter(self.map.values())
+                    self.f0 = next(it)[0]
+                    for key, _ in it:
+                        if _compare(self.f0, key) * self.sign > 0:
+                            self.f0 = key
+            else:
+                self.map[k][1] = count
         elif self.fn in ("sum", "avg"):
             self.sum = self.sum - v
             if self.typ in _BITS:
@@ -76,11 +146,9 @@ class _Agg:
             return None
         if self.fn == "sum":
             return self.sum
-        if self.fn == "min":
-            return min(self.values)
-        if self.fn == "max":
-            return max(self.values)
-        if self.typ in ("double", "float"):
+        if self.fn in ("min", "max"):
+            return self.f0
+        if self.floating:
             return self.sum / self.count
         q = _tdiv(self.sum, self.count)
         return q if self.typ == "long" else _wrap(q, _BITS[self.typ])
@@ -110,7 +178,8 @@ class OverRef:
 
     # ---- function.createAccumulators / accumulate / retract / setAggregationResults
     def _create(self):
-        return [_Agg(f, self.column_types[c] if f != "count_star" else "long") for f, c in self.aggregates]
+        return [_Agg(f, self.column_types[c] if f != "count_star" else "long", retract=self.bounded)
+                for f, c in self.aggregates]
 
     def _accumulate(self, acc, row):
         for a, (f, c) in zip(acc, self.aggregates):

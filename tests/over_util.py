@@ -2,6 +2,7 @@
 process(keys, rowtimes, columns, nulls) / watermark(wm) -> [(key, rowtime, ordinal, [values])] (the restatement
 tests/over_ref.py and the GPU operator alike), and seeded streams."""
 import json
+import math
 import os
 
 import numpy as np
@@ -130,7 +131,9 @@ def by_key(rows):
 
 
 def assert_same_rows(got, exp, rtol, ordinals=True):
-    """Per key in (rowtime, arrival) order; integers and NULLs exact, floats within rtol."""
+    """Per key in (rowtime, arrival) order; integers and NULLs exact, floats within rtol.  Finite float
+    expectations only: a relative tolerance cannot match a NaN or an infinity (and does not see a zero's sign); such
+    values are compared by bits, tests/over_edges_util.py::same_rows_bits."""
     g, e = by_key(got), by_key(exp)
     assert sorted(g) == sorted(e), (len(g), len(e))
     for k in e:
@@ -139,6 +142,7 @@ def assert_same_rows(got, exp, rtol, ordinals=True):
             assert gt == et and (go == eo or not ordinals), (k, gt, go, et, eo)
             for q, (a, b) in enumerate(zip(gv, ev)):
                 if isinstance(b, float) and a is not None:
+                    assert math.isfinite(b), ("assert_same_rows cannot judge a non-finite expectation", k, gt, q, a, b)
                     assert abs(a - b) <= rtol * abs(b), (k, gt, q, a, b)
                 else:
                     assert a == b and type(a) is type(b), (k, gt, q, a, b)

@@ -134,3 +134,119 @@ class _Wrap:
 
     def watermark(self, wm):
         return self.r.watermark(wm)
+
+
+# ---------------------------------------------------------------- Double specials, zero signs (answers by hand from the Scala)
+import struct  # noqa: E402
+
+NAN, INF, DBL_MAX = float("nan"), float("inf"), 1.7976931348623157e308
+ALL_KINDS = ["bounded_rows", "bounded_range", "unbounded_rows", "unbounded_range"]
+
+
+def _b(v):
+    """a result as comparable bits: None, or the 64 bits with every NaN the canonical one"""
+    if v is None:
+        return None
+    return "nan" if v != v else struct.unpack("<q", struct.pack("<d", v))[0]
+
+
+PZ, NZ = _b(0.0), _b(-0.0)
+
+
+def _doubles(kind, preceding, values, fns=("sum", "min", "max", "avg"), wms=None):
+    """one key, row times 1, 2, ..; per function the emitted results as bits, over all watermarks"""
+    r = OverRef(kind, preceding, ["double"], [(f, 0) for f in fns])
+    n = len(values)
+    r.process([1] * n, list(range(1, n + 1)), [[0.0 if v is None else v for v in values]],
+              [1 if v is None else 0 for v in values])
+    rows = [row for wm in (wms or [LMAX]) for row in r.watermark(wm)]
+    assert [row[1] for row in rows] == list(range(1, n + 1))
+    return {f: [_b(row[3][q]) for row in rows] for q, f in enumerate(fns)}
+
+
+def test_double_compare_order():
+    from tests.over_ref import _compare, double_bits
+    assert PZ == 0 and NZ == -(1 << 63) and double_bits(-NAN) == double_bits(NAN) == 0x7FF8000000000000
+    order = [-INF, -1.5, -0.0, 0.0, 1.5, DBL_MAX, INF, NAN]
+    for i, a in enumerate(order):
+        for j, b in enumerate(order):
+            assert _compare(a, b) == (i > j) - (i < j), (a, b)
+    assert _compare(3, 3) == 0 and _compare(-2, 5) == -1
+
+
+def test_bounded_max_keeps_a_stale_nan_after_its_retraction():
+    # MaxAggFunctionWithRetract.scala:84: `v == acc.f0` is false for NaN, so the map is not rescanned when the NaN
+    # leaves: ROWS 1 PRECEDING over NaN, 1, 2, 3 -- the frames {1, 2} and {2, 3} hold no NaN and still give NaN
+    for wms in (None, [3, LMAX], [1, 2, 3, 4]):
+        got = _doubles("bounded_rows", 1, [NAN, 1.0, 2.0, 3.0], wms=wms)
+        assert got["max"] == ["nan"] * 4
+        assert got["min"] == ["nan", _b(1.0), _b(1.0), _b(2.0)]      # MIN: NaN is the greatest value, never stale
+        assert got["sum"] == ["nan"] * 4 and got["avg"] == ["nan"] * 4
+    # ... until the map empties (:78-80 resets f0): frames {NaN}, {NaN, 1}, {1, NULL}, {NULL, NULL}, {NULL, 5}
+    got = _doubles("bounded_rows", 1, [NAN, 1.0, None, None, 5.0], fns=("max", "min"))
+    assert got["max"] == ["nan", "nan", "nan", None, _b(5.0)]
+    assert got["min"] == ["nan", _b(1.0), _b(1.0), None, _b(5.0)]
+    # RANGE 1 ms PRECEDING, row times 1 .. 4: the same frames
+    got = _doubles("bounded_range", 1, [NAN, 1.0, 2.0, 3.0])
+    assert got["max"] == ["nan"] * 4 and got["min"] == ["nan", _b(1.0), _b(1.0), _b(2.0)]
+
+
+@pytest.mark.parametrize("kind", ALL_KINDS)
+def test_min_ignores_nan_and_max_takes_it(kind):
+    # a frame that grows only (ROWS / RANGE 10 over 3 rows, or unbounded): compare(NaN, x) > 0 for every x
+    neg_nan = struct.unpack("<d", struct.pack("<Q", 0xFFF8000000000000))[0]     # Inf - Inf on x86: the sign bit set
+    for nan in (NAN, neg_nan):
+        got = _doubles(kind, 10, [nan, -INF, 1.0], fns=("min", "max"))
+        assert got["min"] == ["nan", _b(-INF), _b(-INF)] and got["max"] == ["nan"] * 3
+        got = _doubles(kind, 10, [1.0, nan, INF], fns=("min", "max"))
+        assert got["min"] == [_b(1.0)] * 3 and got["max"] == [_b(1.0), "nan", "nan"]
+
+
+@pytest.mark.parametrize("kind", ALL_KINDS)
+def test_zero_signs_in_min_and_max_in_both_arrival_orders(kind):
+    # Double.compare(-0.0, 0.0) < 0: MIN takes -0.0, MAX takes +0.0, whichever came first
+    got = _doubles(kind, 10, [0.0, -0.0], fns=("min", "max"))
+    assert got["min"] == [PZ, NZ] and got["max"] == [PZ, PZ]
+    got = _doubles(kind, 10, [-0.0, 0.0], fns=("min", "max"))
+    assert got["min"] == [NZ, NZ] and got["max"] == [NZ, PZ]
+
+
+def test_retracting_a_zero_rescans_by_numeric_equality():
+    # ROWS 1 PRECEDING over -0.0, 0.0, 0.0: the third row retracts -0.0; -0.0 == f0 (numeric), the map {0.0} is
+    # rescanned.  Over 0.0, -0.0, -0.0 the MAX 0.0 leaves the same way.
+    assert _doubles("bounded_rows", 1, [-0.0, 0.0, 0.0], fns=("min", "max")) == {"min": [NZ, NZ, PZ], "max": [NZ, PZ, PZ]}
+    assert _doubles("bounded_rows", 1, [0.0, -0.0, -0.0], fns=("min", "max")) == {"min": [PZ, NZ, NZ], "max": [PZ, PZ, NZ]}
+
+
+@pytest.mark.parametrize("kind", ALL_KINDS)
+def test_sum_of_negative_zeros_is_positive_zero(kind):
+    # numeric.zero is +0.0 and 0.0 + -0.0 = +0.0 (SumWithRetractAggFunction.scala:43-52, SumAggFunction.scala:39-50)
+    got = _doubles(kind, 1, [-0.0, -0.0, None, -0.0], fns=("sum", "avg", "min"))
+    assert got["sum"] == [PZ] * 4 and got["avg"] == [PZ] * 4 and got["min"] == [NZ] * 4
+
+
+def test_a_retracted_infinity_leaves_a_sticky_nan():
+    # ROWS 1 PRECEDING over Inf, 1, 2, 3: Inf, Inf + 1, then (Inf - Inf) + 2 = NaN, and NaN from there on
+    for wms in (None, [2, LMAX], [3, LMAX]):
+        got = _doubles("bounded_rows", 1, [INF, 1.0, 2.0, 3.0, 4.0], wms=wms)
+        assert got["sum"] == [_b(INF), _b(INF), "nan", "nan", "nan"]
+        assert got["max"] == [_b(INF), _b(INF), _b(2.0), _b(3.0), _b(4.0)]
+    got = _doubles("bounded_range", 0, [INF, 1.0, 2.0])     # RANGE 0: each row alone
+    assert got["sum"] == [_b(INF), "nan", "nan"]
+    got = _doubles("bounded_rows", 1, [INF, -INF, 2.0], fns=("sum",))   # Inf + -Inf
+    assert got["sum"] == [_b(INF), "nan", "nan"]
+    got = _doubles("bounded_rows", 1, [-INF, 1.0, 2.0], fns=("sum",))
+    assert got["sum"] == [_b(-INF), _b(-INF), "nan"]
+    for kind in ("unbounded_rows", "unbounded_range"):      # nothing is retracted
+        assert _doubles(kind, 0, [INF, 1.0, 2.0], fns=("sum",))["sum"] == [_b(INF)] * 3
+
+
+def test_an_overflowed_sum_is_a_sticky_infinity():
+    # ROWS 1 PRECEDING over MAX, MAX, 1, 2: MAX, MAX + MAX = Inf, (Inf - MAX) + 1 = Inf, and Inf from there on
+    for wms in (None, [2, LMAX], [3, LMAX]):
+        got = _doubles("bounded_rows", 1, [DBL_MAX, DBL_MAX, 1.0, 2.0, 3.0], wms=wms)
+        assert got["sum"] == [_b(DBL_MAX), _b(INF), _b(INF), _b(INF), _b(INF)]
+        assert got["avg"] == [_b(DBL_MAX), _b(INF), _b(INF), _b(INF), _b(INF)]
+        assert got["max"] == [_b(DBL_MAX), _b(DBL_MAX), _b(DBL_MAX), _b(2.0), _b(3.0)]
+    got = _doubles("bounded_rows", 1, [DBL_MAX, DBL_MAX, 1.0, -INF, 3.0], fns=("sum",))
+    assert got["sum"] == [_b(DBL_MAX), _b(INF), _b(INF), "nan", "nan"]
